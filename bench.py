@@ -14,6 +14,13 @@ A step = one pass of the hot path over the rank's batch:
                  -> polyphase filter bank + 800-point FFT (fused, in LDS) -> per-carrier RRC resampler to 72 kHz ->
                  timing/decision -> lower MAC, every carrier cut into 3932-sample timing chunks
 
+A plain run does only what its headline needs: set-up, warm-up, the timed steps, the result line.
+  --full         adds what takes work of its own after the clock stopped: the CPU baselines (unless
+                 --no-cpu), the measured read floor and the committed PMC traffic in "roofline", and the
+                 last step's decoded-block statistics ("decoded_last_step")
+  --dump-outputs DIR  writes what the last timed step computed (a fixed, seeded sample of its rows,
+                 the written parts only) as DIR/<name>.npy; the inputs depend only on the arguments
+
 Launch: python bench.py --gpus 1 --steps 5 --warmup 2
         python bench.py --gpus N ...   (starts torch.distributed.run --nproc-per-node N as a child)
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
@@ -51,8 +58,14 @@ def parse():
                     help="wideband: 20 MSps samples per rank per step (C3: 0.5 s)")
     ap.add_argument("--channels", type=int, default=8192, help="channels per rank")
     ap.add_argument("--samples", type=int, default=131072, help="samples per channel chunk")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU-baseline budget (rank 0)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need, after the timed steps: the CPU baselines, the "
+                         "read floor and the committed PMC traffic of the roofline, the decoded-block statistics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64; a fixed, "
+                         "seeded sample of the rows, at most 64 MB in all)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: CPU-baseline budget (rank 0)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--iq", choices=("cf32", "sc16"), default="cf32",
                     help="etsi: input sample format in HBM (sc16 = the BladeRF wire format, 4 B/sample)")
     ap.add_argument("--pipeline", choices=("auto", "on", "off"), default="auto",
@@ -293,6 +306,96 @@ def time_steps(step, steps, warmup, world, sync, on_timed=None):
     return time.perf_counter() - t0
 
 
+DUMP_BYTES = 56_000_000   # of the 64 MB a dump may take (its row indices included), shared by the row groups
+DUMP_SEED = 20240531
+
+
+def _upto(n, length, start=0):
+    """[rows, length] bool: start <= j < start + n[row]."""
+    j = torch.arange(length, device=n.device)[None, :]
+    return (j >= start) & (j < start + n[:, None])
+
+
+def _keep(t, mask):
+    """t where mask (broadcast over t's trailing dims), 0 elsewhere: the buffers are torch.empty, so only
+    the written parts of a row compare from run to run."""
+    while mask.dim() < t.dim():
+        mask = mask[..., None]
+    return torch.where(mask, t, torch.zeros((), dtype=t.dtype, device=t.device))
+
+
+def _demod_rows(r, sym, soft, hard, nsym, off=0):
+    """Rows r of a demod's outputs: nsym symbols, nsym - 1 dibits and their soft bits, from column off."""
+    ns = nsym[r].long()
+    nh = (ns - 1).clamp(min=0)
+    L = hard.shape[1] - off
+    return {"nsym": ns, "sym": _keep(sym[r, off:], _upto(ns, L)), "soft": _keep(soft[r, 2 * off:], _upto(2 * nh, 2 * L)),
+            "hard": _keep(hard[r, off:], _upto(nh, L))}
+
+
+def _etsi_lmac_rows(step, r):
+    """Rows r of the ETSI lower MAC's outputs: nburst bursts, nblock blocks, each block's type-1 bits."""
+    nb, nk = step.nburst[r].long(), step.nblock[r].long()
+    live = _upto(nk, _hip.ETSI_MAXJ)
+    blocks = _keep(step.blocks[r], live)
+    # type-1 bits per block kind (the rest of a type1 row is padding)
+    bits = torch.tensor((268, 124, 60), device=nk.device)[blocks[..., 0].clamp(0, 2).long()] * live
+    return {"nburst": nb, "bursts": _keep(step.bursts[r], _upto(nb, _hip.ETSI_MAXB)), "nblock": nk, "blocks": blocks,
+            "type1": _keep(step.type1[r], torch.arange(268, device=nk.device)[None, None, :] < bits[..., None])}
+
+
+def last_outputs(step):
+    """What a caller of the timed path holds after its last step, as row groups [(file prefix, rows, fn)]: fn(r)
+    gives {name: device tensor} of the rows r (an index tensor), unwritten parts zeroed."""
+    if isinstance(step, CompatStep):
+        ln = step.lanes[(step.k - 1) % len(step.lanes)]
+
+        def compat(r):
+            ns = ln.nsym[r].long()   # nsym soft symbols (complex128 pairs), nsym - 1 hard ones
+            L = ln.hard.shape[1]
+            out = {"nsym": ns, "soft": _keep(ln.soft[r], _upto(ns, L)),
+                   "hard": _keep(ln.hard[r], _upto((ns - 1).clamp(min=0), L))}
+            rec = _keep(ln.rec[r], _upto(ln.nsync[r].long(), _hip.MAX_SYNC))
+            nbits = rec[..., _hip.F_NBITS] * (rec[..., _hip.F_VALID] != 0)   # 0 for a slot decode() skips
+            j = torch.arange(510, device=rec.device)[None, None, :]
+            out.update(nsync=ln.nsync[r], rec=rec, frame_bits=_keep(ln.fb[r], j < nbits[..., None]),
+                       burst_bits=_keep(ln.bb[r], nbits >= 510))
+            return out
+        return [("", step.C, compat)]
+    if hasattr(step, "wf"):   # wideband: the waterfall rows, and per (carrier, chunk) the timing + lower MAC
+        return [("", step.C, lambda r: {**_demod_rows(r, step.sym, step.soft, step.hard, step.nsym),
+                                        **_etsi_lmac_rows(step, r)}),
+                ("waterfall_", step.nfr, lambda r: {"waterfall": step.wf[r]})]
+    # etsi: the demod outputs of the last step's buffer (streaming rows start ETSI_RESERVE dibits in)
+    if step.stream or (step.pipelined and step.demod_mode != "split"):
+        sym, soft, hard, nsym = step.bufs[((step.k if step.pipelined else step.kchunk) - 1) & 1]
+    else:
+        sym, soft, hard, nsym = step.sym, step.soft, step.hard, step.nsym
+    off = _hip.ETSI_RESERVE if step.stream else 0
+    return [("", step.C, lambda r: {**_demod_rows(r, sym, soft, hard, nsym, off), **_etsi_lmac_rows(step, r)})]
+
+
+def dump_outputs(step, path, dev):
+    """Write last_outputs(step) as path/<name>.npy: float32, or float64 for 32- and 64-bit integers and
+    doubles (exact).  Each row group keeps a fixed, seeded sample of its rows (all of them where they
+    fit), listed in path/<group>rows.npy, so that the files of two runs with the same arguments hold
+    the same rows."""
+    def host(t):
+        wide = t.dtype in (torch.int32, torch.int64, torch.float64)
+        return t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+
+    os.makedirs(path, exist_ok=True)
+    groups = last_outputs(step)
+    for prefix, rows, fn in groups:
+        one = {k: host(v) for k, v in fn(torch.zeros(1, dtype=torch.long, device=dev)).items()}
+        per_row = sum(v.nbytes for v in one.values()) + 8
+        n = max(1, min(rows, DUMP_BYTES // len(groups) // per_row))
+        pick = np.arange(rows) if n == rows else np.sort(np.random.default_rng(DUMP_SEED).choice(rows, n, replace=False))
+        np.save(os.path.join(path, prefix + "rows.npy"), pick.astype(np.float64))
+        for k, v in fn(torch.from_numpy(pick).to(dev)).items():
+            np.save(os.path.join(path, k + ".npy"), host(v))
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -411,6 +514,8 @@ def main():
     elapsed = max_over_ranks(elapsed, dev if backend == "nccl" else None, force=force)
     ms_step = elapsed / a.steps * 1e3
     value = aggregate_msps(C * N, world, a.steps, elapsed)
+    if a.dump_outputs:   # rank 0's files in the directory itself, the other ranks' beside them
+        dump_outputs(step, a.dump_outputs if rank == 0 else os.path.join(a.dump_outputs, f"rank{rank}"), dev)
 
     if rank == 0:
         if hasattr(step, "stage_bytes"):   # several comparable stages: the slowest one is dominant
@@ -423,10 +528,11 @@ def main():
         launch_ms = kms / max(1, kcnt)
         units_per_launch = C * N
         achieved = per_sample * units_per_launch / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
-        floor = read_floor(c, step) if hasattr(step, "floor_args") else None
-        cpu = None if a.no_cpu else cpu_baseline(a, step)
+        # --full only: launches, file reads and host work of their own, after the clock stopped
+        floor = read_floor(c, step) if a.full and hasattr(step, "floor_args") else None
+        cpu = None if a.no_cpu or not a.full else cpu_baseline(a, step)
         traffic = traffic_from_profiles(ksym, step.workload_key() if hasattr(step, "workload_key") else
-                                        f"{C} channels x {N} {a.iq if a.chain == 'etsi' else 'cf32'}")
+                                        f"{C} channels x {N} {a.iq if a.chain == 'etsi' else 'cf32'}") if a.full else None
         out = {
             "metric": "IQ Msamples/s demod+Viterbi; real-time 25 kHz TETRA channels @1/2/4/8 GPU",
             "value": round(value, 3),
@@ -462,8 +568,7 @@ def main():
                 "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                 # HBM bytes per launch from this round's PMC summary of the same sources (or null), and
                 # where that number came from (or why there is none)
-                "traffic": traffic["bytes"] if traffic else None,
-                "traffic_source": traffic,
+                **({"traffic": traffic["bytes"], "traffic_source": traffic} if traffic else {}),
                 "launch_ms": round(launch_ms, 4), "algorithmic_bytes_per_launch": per_sample * units_per_launch,
                 "kernel_symbol": ksym,
                 # the same HBM read pattern with no arithmetic (k_read_floor), measured in this run:
@@ -472,8 +577,9 @@ def main():
             },
             "stages_ms_per_step": {k: round(v[0] / a.steps, 4) for k, v in prof.items()},
             # the last step's decoded blocks (read back after the timed region): the chain's work done
-            **({"decoded_last_step": step.quality()} if hasattr(step, "quality") else {}),
-            "cpu_baseline": cpu,
+            **({"decoded_last_step": step.quality()} if a.full and hasattr(step, "quality") else {}),
+            **({"cpu_baseline": cpu} if a.full else {}),
+            "full": a.full,
         }
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

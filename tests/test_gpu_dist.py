@@ -29,7 +29,7 @@ def test_torchrun_two_ranks_bench():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", "2", "--channels", str(C), "--samples", str(N),
-           "--steps", str(steps), "--warmup", "1", "--no-cpu", "--cells", "given"]
+           "--steps", str(steps), "--warmup", "1", "--full", "--no-cpu", "--cells", "given"]
     env = dict(os.environ, TETRA_BENCH_DIST="gloo", OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -54,7 +54,7 @@ def test_torchrun_one_rank_rccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", "1", "--channels", str(C), "--samples", str(N),
-           "--steps", str(steps), "--warmup", "1", "--no-cpu", "--cells", "given"]
+           "--steps", str(steps), "--warmup", "1", "--full", "--no-cpu", "--cells", "given"]
     env = dict(os.environ, TETRA_BENCH_DIST="nccl", TETRA_BENCH_FORCE_DIST="1", OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -73,7 +73,7 @@ def test_bare_gpus2_self_launches_two_ranks():
     prints the one line, with n_gpus 2 and a world-2 process group."""
     C, N, steps = 256, 131072, 3
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--channels", str(C),
-           "--samples", str(N), "--steps", str(steps), "--warmup", "1", "--no-cpu", "--cells", "given"]
+           "--samples", str(N), "--steps", str(steps), "--warmup", "1", "--full", "--no-cpu", "--cells", "given"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(TETRA_BENCH_DIST="gloo", OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=110)

@@ -49,7 +49,7 @@ run)
     for i in $(seq 1 ${AB_ROUNDS:-3}); do
         for L in "$@"; do
             n=$(basename $L .so)
-            TETRA_HIP_LIB=$R/$L timeout -k 10 200 python -u bench.py --no-cpu --steps 30 ${AB_ARGS:---pipeline off} \
+            TETRA_HIP_LIB=$R/$L timeout -k 10 200 python -u bench.py --full --no-cpu --steps 30 ${AB_ARGS:---pipeline off} \
                 > $O/$n.$i.log 2>&1
             summ "$n" $O/$n.$i.log
         done
@@ -60,7 +60,7 @@ env)
         k=0
         for E in "$@"; do
             k=$((k + 1))
-            env $E timeout -k 10 200 python -u bench.py --no-cpu --steps 30 ${AB_ARGS} > $O/$k.$i.log 2>&1
+            env $E timeout -k 10 200 python -u bench.py --full --no-cpu --steps 30 ${AB_ARGS} > $O/$k.$i.log 2>&1
             summ "$E" $O/$k.$i.log
         done
     done ;;
