@@ -80,7 +80,8 @@ int tetra_mark(tetra_ctx *ctx, int tag);
 
 /* =====================================================================================
  * Compat demod -- bit-compatible with SignalProcessor (processor.py:221-273) in its default
- * (sequential) form; the opt-in latency mode (TETRA_COMPAT_BLOCKED) is within fp32 noise only
+ * (sequential) form and in the opt-in time-tiled form (TETRA_COMPAT_TILED); the opt-in latency mode
+ * (TETRA_COMPAT_BLOCKED) is within fp32 noise only
  * ===================================================================================== */
 
 /* Filter design and control decisions are made by the host (the same scipy.signal design calls
@@ -93,7 +94,8 @@ typedef struct tetra_compat_plan {
     int32_t ntaps;        /* butter(4) -> 5 */
     int32_t sps;          /* int(rate/18000) (processor.py:183) */
     int32_t phase_step;   /* max(1, sps//8) (processor.py:194) */
-    int32_t flags;        /* TETRA_COMPAT_*: 0 = scipy's sequential order (bit-exact), BLOCKED = latency mode */
+    int32_t flags;        /* TETRA_COMPAT_*: 0 = scipy's sequential order (bit-exact), TILED = the same results
+                           * from time tiles with verified boundaries, BLOCKED = latency mode (not bit-exact) */
     int32_t reserved;
     double fs_dec;        /* sample rate after decimation: time base of frequency_shift */
     float sos_f32[24];    /* cheby1(8, 0.05, 0.8/q) SOS [4][6] as complex64 real parts */
@@ -112,16 +114,35 @@ typedef struct tetra_compat_plan {
  * channels, q <= 16 and N + 54 <= 262144 samples (TETRA_E_INVALID outside those limits); ~40x lower
  * latency for one channel but NOT bit-exact: the decimator ends up to ~1.5e-5 from scipy's fp32
  * state near the chunk start, so a decision whose phase margin is ~1e-6 rad can flip (measured: 3 in
- * 1.6 M symbols).  The component entry point tetra_decimate is always sequential. */
+ * 1.6 M symbols).  The component entry point tetra_decimate is always sequential.
+ * TETRA_COMPAT_TILED opts into the exact time-tiled decimator: every tile of the fp32 sosfiltfilt is
+ * run at once from an all-zero state `warm` samples early, the state it reaches at its first sample
+ * is compared bit for bit with the state the previous tile ended in, and a tile that differs is run
+ * again from that state -- so the result is the sequential one by construction, and only the speed
+ * depends on the input (noisy captures: no reruns at the built-in lengths; noiseless input such as a
+ * constant row: every tile rerun, as slow as the sequential form).  It applies to complex64 input,
+ * 1 <= C <= 64, q in 7..10 and N longer than one tile; anywhere else, and together with
+ * TETRA_COMPAT_BLOCKED, the flag is ignored (the sequential kernels give the same result).  The
+ * filtfilt stage stays sequential. */
 #define TETRA_COMPAT_SEQUENTIAL 1   /* the scipy-exact sequential passes (the default) */
 #define TETRA_COMPAT_BLOCKED    2   /* the time-blocked latency mode (opt-in, not bit-exact) */
+#define TETRA_COMPAT_TILED      4   /* tetra_compat_plan.flags: the exact time-tiled decimator (opt-in) */
 
 /* Host-only (no device needed): the kernels tetra_demod_compat would run for `plan` on a [C][N]
  * batch, as TETRA_FORM_* bits in *forms. */
 #define TETRA_FORM_DEC_BLOCKED  1   /* decimate: time-blocked (else scipy's sequential order) */
 #define TETRA_FORM_LF_BLOCKED   2   /* filtfilt: time-blocked (else scipy's sequential order) */
 #define TETRA_FORM_POW_PREPASS  4   /* extract_symbols: |y|^2 first in parallel (exact either way) */
+#define TETRA_FORM_DEC_TILED    8   /* tetra_compat_forms: decimate runs time-tiled (bit-identical to sequential) */
 int tetra_compat_forms(const tetra_compat_plan *plan, size_t C, size_t N, int32_t *forms);
+/* tile / warm-up lengths of the tiled decimator on this context; 0, 0 = the built-in defaults.
+ * Multiples of 64, tile >= 64, warm >= 64 (TETRA_E_INVALID otherwise).  tetra_compat_forms is
+ * host-only and answers for the built-in tile length. */
+int tetra_compat_set_tiles(tetra_ctx *ctx, int tile, int warm);
+/* the last tiled decimate on this context, summed over streams: stats[0..3] = forward tiles checked,
+ * forward tiles rerun, backward tiles checked, backward tiles rerun (all 0 if it ran sequential kernels).
+ * A stream is one real component of one channel; every tile but a stream's first is checked. */
+int tetra_compat_tile_stats(tetra_ctx *ctx, int32_t *stats);
 
 /* Fused process() over a batch of C equal-length chunks.
  *   iq        [C][N] complex, format iq_fmt (TETRA_CF32 for SC16-derived capture data)
@@ -148,6 +169,9 @@ int tetra_compat_blocked_table(const tetra_compat_plan *plan, int which, double 
 /* scipy.signal.decimate(x, q) as called at processor.py:254: out [C][ceil(N/q)] in iq_fmt. */
 int tetra_decimate(tetra_ctx *ctx, const tetra_compat_plan *plan, const void *iq, int iq_fmt,
                    size_t C, size_t N, void *out);
+/* scipy.signal.decimate as tetra_decimate, on the tiled kernels where they apply. */
+int tetra_decimate_tiled(tetra_ctx *ctx, const tetra_compat_plan *plan, const void *iq, int iq_fmt,
+                         size_t C, size_t N, void *out);
 /* frequency_shift (processor.py:85-100): out [C][N] complex128. */
 int tetra_frequency_shift(tetra_ctx *ctx, const void *iq, int iq_fmt, size_t C, size_t N,
                           const double *mix_c, double fs, void *out);

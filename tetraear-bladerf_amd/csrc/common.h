@@ -34,6 +34,7 @@ enum Slot {
     S_W17,                                                 // compat time-blocked filtfilt: tile states
     S_W18,                                                 // compat latency mode: extract_symbols' |y|^2 rows
     S_W19,                                                 // compat, few channels: the mixed rows filtfilt reads
+    S_W20,                                                 // compat time-tiled decimator: counters, tile states
     S_COUNT
 };
 
@@ -67,6 +68,8 @@ struct tetra_ctx {
     double sosb_coef[24] = {0};        // ... built from these SOS rows (the plan is a public struct:
     bool sosb_valid = false;           //     the same q may come with other coefficients)
     const void *sosb_dev = nullptr;    // ... to this address (slot S_W16; cleared when ws() reallocates it)
+    int tl_tile = 0, tl_warm = 0;      // compat time-tiled decimator: tile / warm-up lengths (0: built-in)
+    bool tl_ran = false;               // ... its last call ran tiled kernels (counters in slot S_W20)
     void *pin = nullptr;               // pinned host arena: small staged copies go through it (Staging)
     size_t pin_cap = 0;
     bool pin_busy = false;             // a copy through the arena may still be in flight
@@ -149,6 +152,13 @@ __device__ __forceinline__ uint2 ld_nt(const uint2 *p) {
     const nt_u2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_u2 *>(p));
     return make_uint2(v.x, v.y);
 }
+
+// Exact time-tiled compat decimator (compat_tiled.hip): whether it applies to a plan and batch shape
+// with tiles of `tile` samples (0: the built-in length), and the run -- complex64 rows [C][N] in,
+// decimate's output to `out` in the strided layout (s_grp, s_n, s_lane) of compat_sos.h's Lay.
+bool tiled_fits(const tetra_compat_plan *P, size_t C, size_t N, int tile);
+int run_decimate_tiled(tetra_ctx *ctx, const tetra_compat_plan *P, const float *x, int C, long N, float *out,
+                       size_t s_grp, size_t s_n, size_t s_lane);
 
 // ETSI channel filter at a non-canonical rate (etsi_rate.hip): plan limits (nullptr = supported),
 // the launch (y [C][M2] to HBM), and the kernel symbol (tetra_etsi_kernel_info).

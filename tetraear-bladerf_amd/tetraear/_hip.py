@@ -40,7 +40,9 @@ class CompatPlan(ctypes.Structure):
 
 
 COMPAT_SEQUENTIAL, COMPAT_BLOCKED = 1, 2   # tetra_compat_plan.flags: 0 = sequential (scipy-exact), 2 = latency mode
+COMPAT_TILED = 4                           # ... 4 = the exact time-tiled decimator
 FORM_DEC_BLOCKED, FORM_LF_BLOCKED, FORM_POW_PREPASS = 1, 2, 4   # tetra_compat_forms bits
+FORM_DEC_TILED = 8
 ETSI_FORCE_GENERIC = 1   # tetra_etsi_plan.flags: run a canonical plan on the generic-rate kernel
 
 
@@ -94,6 +96,9 @@ def _bind(L):
         "tetra_compat_symbols": (ctypes.c_int64, [ctypes.POINTER(CompatPlan), _sz]),
         "tetra_compat_blocked_table": (_i32, [ctypes.POINTER(CompatPlan), _i32, _vp]),
         "tetra_compat_forms": (_i32, [ctypes.POINTER(CompatPlan), _sz, _sz, _i32p]),
+        "tetra_compat_set_tiles": (_i32, [_vp, _i32, _i32]),
+        "tetra_compat_tile_stats": (_i32, [_vp, _i32p]),
+        "tetra_decimate_tiled": (_i32, [_vp, ctypes.POINTER(CompatPlan), _vp, _i32, _sz, _sz, _vp]),
         "tetra_demod_compat": (_i32, [_vp, ctypes.POINTER(CompatPlan), _vp, _i32, _sz, _sz, _vp, _vp, _vp, _vp, _vp,
                                       _sz, _i32p]),
         "tetra_decimate": (_i32, [_vp, ctypes.POINTER(CompatPlan), _vp, _i32, _sz, _sz, _vp]),

@@ -96,7 +96,8 @@ def _fill(arr, vals):
         arr[i] = v
 
 
-DECIMATORS = {"auto": 0, "sequential": _hip.COMPAT_SEQUENTIAL, "blocked": _hip.COMPAT_BLOCKED}
+DECIMATORS = {"auto": 0, "sequential": _hip.COMPAT_SEQUENTIAL, "blocked": _hip.COMPAT_BLOCKED,
+              "tiled": _hip.COMPAT_TILED}
 
 
 def default_decimator():
@@ -111,13 +112,15 @@ def default_decimator():
 
 def compat_forms(plan, C, N):
     """The kernels tetra_demod_compat runs for `plan` on a [C, N] batch (host-only query):
-    {"decimate": "blocked"|"sequential", "filtfilt": ..., "power_prepass": bool}."""
+    {"decimate": "blocked"|"tiled"|"sequential", "filtfilt": "blocked"|"sequential",
+    "power_prepass": bool}."""
     import ctypes
     f = ctypes.c_int32(0)
     if _hip.lib().tetra_compat_forms(plan, int(C), int(N), ctypes.byref(f)) != 0:
         raise ValueError("tetra_compat_forms: invalid plan")
     v = f.value
-    return {"decimate": "blocked" if v & _hip.FORM_DEC_BLOCKED else "sequential",
+    dec = "blocked" if v & _hip.FORM_DEC_BLOCKED else "tiled" if v & _hip.FORM_DEC_TILED else "sequential"
+    return {"decimate": dec,
             "filtfilt": "blocked" if v & _hip.FORM_LF_BLOCKED else "sequential",
             "power_prepass": bool(v & _hip.FORM_POW_PREPASS)}
 
@@ -135,7 +138,11 @@ def compat_plan(sample_rate, n, fmt, bandwidth=25000, decimator="auto", real=Fal
     to the reference; "blocked" is the opt-in latency mode -- 256-/128-sample tiles recursed in
     parallel, ~40x lower latency for one chunk, but only within the cheby1 filter's fp32 noise of
     scipy (up to ~1.5e-5 on .symbols near the chunk start; a decision with a ~1e-6 rad margin can
-    flip), so it is never chosen for the caller.
+    flip), so it is never chosen for the caller; "tiled" is the opt-in exact time-tiled decimator --
+    every tile run at once from a zero state a warm-up early, its state at the tile start compared
+    bit for bit with the previous tile's end state and the tile rerun when they differ, so the result
+    is the sequential one and only the speed depends on the input (complex64 chunks longer than one
+    tile, up to 64 channels, q 7..10; the sequential kernels anywhere else).
     ``real``: the samples are real (decimate's initial state in the real dtype).  ``cache=False``
     returns a private plan the caller may modify."""
     key = (float(sample_rate), int(n), int(fmt), bandwidth, decimator, bool(real))
@@ -206,9 +213,21 @@ class SignalProcessor:
         if decimator not in DECIMATORS:
             raise ValueError(f"decimator must be one of {sorted(DECIMATORS)}, not {decimator!r}")
         # compat process(): the decimator form (compat_plan); "auto"/"sequential" is scipy's exact
-        # order for every batch size, "blocked" the opt-in latency mode (not bit-exact)
+        # order for every batch size, "tiled" the same results from verified time tiles (opt-in),
+        # "blocked" the opt-in latency mode (not bit-exact)
         self.decimator = decimator
         self._etsi = None
+
+    @property
+    def tile_stats(self):
+        """Counters of the last tiled decimate on this thread's context, summed over streams (one per
+        real component of a channel): tiles checked / rerun in the forward and the backward pass.
+        All zero when that call ran the sequential kernels."""
+        import ctypes
+        st = (ctypes.c_int32 * 4)()
+        c = _hip.ctx()
+        c.check(c.lib.tetra_compat_tile_stats(c.handle, st), "tetra_compat_tile_stats")
+        return dict(zip(("fwd_checked", "fwd_rerun", "bwd_checked", "bwd_rerun"), (int(v) for v in st)))
 
     # --------------------------------------------------------------- component methods
     def resample(self, samples, target_rate):

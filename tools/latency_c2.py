@@ -5,7 +5,10 @@ call, then decode) -- the per-chunk latency against the chunk's 54.6 ms of air a
 Times, per chunk (median of --reps calls after warm-up):
   * etsi:   SignalProcessor(mode="etsi").process(x) + TetraDecoder(mode="etsi").decode(hard)
   * compat: SignalProcessor().process(x, f) + TetraDecoder().decode(hard)   (the reference's semantics,
-            the default scipy-exact form); compat_blocked: the opt-in latency mode's process()
+            the default scipy-exact form); compat_blocked: the opt-in latency mode's process();
+            compat_tiled: the opt-in exact time-tiled decimator's process() on the same chunk, and
+            compat_tiled_worstcase on a constant-valued chunk (every tile rerun), each with the
+            decimator's tile counters (SignalProcessor.tile_stats)
   * batch:  EtsiReceiver.demod_batch + EtsiLowerMac.decode_batch over C host channels at once
 Host buffers in and out (H2D / D2H included): this is the drop-in's latency, not the HBM-resident
 throughput bench.py reports.  usage: python tools/latency_c2.py [--reps 50]
@@ -63,6 +66,14 @@ def main():
     out["compat_decode_ms"] = med_ms(lambda: dc.decode(hc), a.reps)
     pb = SignalProcessor(fs, decimator="blocked")   # the opt-in latency mode (not bit-exact)
     out["compat_blocked_process_ms"] = med_ms(lambda: pb.process(x, 1171.875), a.reps)
+    pt = SignalProcessor(fs, decimator="tiled")   # the opt-in exact time-tiled decimator
+    out["compat_tiled_process_ms"] = med_ms(lambda: pt.process(x, 1171.875), a.reps)
+    out["compat_tiled_stats"] = pt.tile_stats
+    out["compat_tiled_equal"] = bool(np.array_equal(pt.process(x, 1171.875), hc) and np.array_equal(pt.symbols, pc.symbols))
+    xc = np.full(N, 0.25 + 0.125j, np.complex64)   # noiseless: no tile's state merges, all are rerun
+    out["compat_tiled_worstcase_ms"] = med_ms(lambda: pt.process(xc, 1171.875), a.reps)
+    out["compat_tiled_worstcase_stats"] = pt.tile_stats
+    out["compat_worstcase_sequential_ms"] = med_ms(lambda: pc.process(xc, 1171.875), a.reps)
 
     rx, mac = EtsiReceiver(), EtsiLowerMac()
     for C in (1, 8, 64):

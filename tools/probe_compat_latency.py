@@ -1,6 +1,6 @@
 """Where one compat process() call's time goes (C2, one 131072-sample chunk from host memory):
-per-stage device times from the library's HIP-event profile (tetra_profile) for the time-blocked and
-the sequential decimator, and the host wall time of the call.  usage: python tools/probe_compat_latency.py"""
+per-stage device times from the library's HIP-event profile (tetra_profile) for the default, the
+sequential and the exact time-tiled decimator, and the host wall time of the call.  usage: python tools/probe_compat_latency.py"""
 import ctypes
 import json
 import os
@@ -31,7 +31,7 @@ def main():
     x = np.ascontiguousarray(iq[0])
     c = _hip.ctx()
     out = {}
-    for dec in ("auto", "sequential"):
+    for dec in ("auto", "sequential", "tiled"):
         p = SignalProcessor(2.4e6, decimator=dec)
         for _ in range(3):
             p.process(x, 1171.875)
