@@ -391,7 +391,12 @@ int tetra_etsi_set_cells(tetra_ctx *ctx, const uint32_t *scramb_init, size_t C);
 /* Lower MAC: burst sync + descramble + deinterleave + depuncture + Viterbi + CRC per channel.
  *   nburst [C], bursts [C][TETRA_ETSI_MAXB][2] (start bit, burst kind),
  *   nblock [C], blocks [C][TETRA_ETSI_MAXJ][4] (block kind, crc_ok, burst index, block index),
- *   type1 [C][TETRA_ETSI_MAXJ][268] decoded type-1 bits. */
+ *   type1 [C][TETRA_ETSI_MAXJ][268] decoded type-1 bits.
+ * Entries past nburst[c] / nblock[c], and a block's type-1 bytes past its length, are not written.
+ * Rows are at most 2050 symbols wide (smax); every one of a row's nsym[c] - 1 dibits is scanned.
+ * Soft bits are expected in [-127, 127], which is what the demodulator writes: a -128 is its own
+ * negative under descrambling (it stays negative where the scrambling bit is 1), in the library and
+ * in the oracle alike. */
 int tetra_lmac_etsi(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym,
                     size_t C, size_t smax, int32_t *nburst, int32_t *bursts, int32_t *nblock,
                     int32_t *blocks, uint8_t *type1);

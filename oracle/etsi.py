@@ -412,6 +412,48 @@ def stream_lengths(d, n):
     return m1, (num // d["down"] + 1 if num >= 0 else 0)
 
 
+class LmacStream:
+    """The lower-MAC half of the streaming receiver for one channel (tetra_lmac_etsi_stream): the
+    dibits the previous chunk's scan left unconsumed go in front of the new ones, the greedy burst
+    scan resumes at the carried bit phase, and the dibits from the first bit not examined (at most
+    RESERVE of them) are carried on.  cell_init None: cell acquisition (the chunk's BSCH blocks
+    first, colour code 0; the last CRC-good one sets the cell)."""
+
+    def __init__(self, rx=None, cell_init=None, maxb=MAXB):
+        self.rx = rx if rx is not None else Receiver()
+        self.maxb = maxb
+        self.tail_hard = np.zeros(0, np.uint8)
+        self.tail_soft = np.zeros(0, np.int8)
+        self.phase = 0
+        self.acquire = cell_init is None
+        # before a BSCH is decoded: colour code 0 (init 3), what every receiver descrambles with
+        self.cell = scramble_init(0, 0, 0) if cell_init is None else int(cell_init)
+
+    def push(self, hard, soft):
+        """One chunk's dibits and soft bits -> dict(bursts, stop, cell, row_bursts, tail): positions
+        of bursts / stop from the chunk's first new dibit (negative: in the carried tail);
+        row_bursts from the row's first dibit, tail = the carried dibits in front of them."""
+        T = len(self.tail_hard)
+        row_h = np.concatenate([self.tail_hard, np.asarray(hard, np.uint8)])
+        row_s = np.concatenate([self.tail_soft, np.asarray(soft, np.int8)])
+        if self.acquire:   # BSCH first (colour code 0): the last CRC-good one sets the cell
+            bursts, stop = self.rx.sync_from(row_h, self.phase, self.maxb)
+            for b0, bk in bursts:
+                if bk == BURST_SB:
+                    t1, ok = self.rx.decode_block(row_s[b0 + 94:b0 + 214], 2, scramble_seq(3, 120))
+                    if ok:
+                        self.cell = bsch_cell_init(t1)
+        bursts, stop = self.rx.sync_from(row_h, self.phase, self.maxb)
+        dec = self.rx.decode_bursts(row_s, bursts, self.cell)
+        d0 = stop // 2
+        th, ts, ph = row_h[d0:], row_s[2 * d0:], stop & 1
+        if len(th) > RESERVE:   # (only past MAXB bursts in one row) keep the last RESERVE dibits
+            th, ts, ph = th[-RESERVE:], ts[-2 * RESERVE:], 0
+        self.tail_hard, self.tail_soft, self.phase = th.copy(), ts.copy(), ph
+        return dict(bursts=[(b - 2 * T, k, dd) for b, k, dd in dec], stop=stop - 2 * T, cell=self.cell,
+                    row_bursts=dec, tail=T)
+
+
 class Stream:
     """CPU restatement of the streaming receiver (tetra_etsi_stream_window + tetra_demod_etsi_stream +
     tetra_lmac_etsi_stream) for one channel: consecutive chunks of one continuous capture decode as
@@ -434,12 +476,11 @@ class Stream:
         self.buf = np.zeros(0, np.complex64)
         self.x_total = self.y_done = 0
         self.trk = np.zeros(1, TRACK)
-        self.tail_hard = np.zeros(0, np.uint8)
-        self.tail_soft = np.zeros(0, np.int8)
-        self.phase = 0
-        self.acquire = cell_init is None
-        # before a BSCH is decoded: colour code 0 (init 3), what every receiver descrambles with
-        self.cell = scramble_init(0, 0, 0) if cell_init is None else int(cell_init)
+        self.lmac = LmacStream(self.rx, cell_init)
+
+    @property
+    def cell(self):
+        return self.lmac.cell
 
     def window(self, n):
         """(s, W, yoff, y_start) of the next chunk of n samples (global sample / y indices)."""
@@ -460,24 +501,6 @@ class Stream:
         assert len(y) == max(m_hi - y_start, 0), (len(y), m_hi, y_start)
         sym, soft, hard, diag = self.rx.timing_stream(y, yoff, self.trk[0:1])
         self.y_done = max(m_hi, self.y_done)
-        # the lower MAC: the tail dibits, then the new ones; scan from the carried phase
-        T = len(self.tail_hard)
-        row_h = np.concatenate([self.tail_hard, hard])
-        row_s = np.concatenate([self.tail_soft, soft])
-        if self.acquire:   # BSCH first (colour code 0): the last CRC-good one sets the cell
-            bursts, stop = self.rx.sync_from(row_h, self.phase)
-            for b0, bk in bursts:
-                if bk == BURST_SB:
-                    t1, ok = self.rx.decode_block(row_s[b0 + 94:b0 + 214], 2, scramble_seq(3, 120))
-                    if ok:
-                        self.cell = bsch_cell_init(t1)
-        bursts, stop = self.rx.sync_from(row_h, self.phase)
-        dec = self.rx.decode_bursts(row_s, bursts, self.cell)
-        d0 = stop // 2
-        th, ts, ph = row_h[d0:], row_s[2 * d0:], stop & 1
-        if len(th) > RESERVE:   # (only past MAXB bursts in one row) keep the last RESERVE dibits
-            th, ts, ph = th[-RESERVE:], ts[-2 * RESERVE:], 0
-        self.tail_hard, self.tail_soft, self.phase = th.copy(), ts.copy(), ph
+        lm = self.lmac.push(hard, soft)
         return dict(y=y, yoff=yoff, window=(s, W), symbols=sym, soft=soft, hard=hard, diag=diag,
-                    bursts=[(b - 2 * T, k, dd) for b, k, dd in dec], cell=self.cell, stop=stop - 2 * T,
-                    track=self.trk.copy())
+                    bursts=lm["bursts"], cell=lm["cell"], stop=lm["stop"], track=self.trk.copy())

@@ -1774,8 +1774,10 @@ __device__ __forceinline__ void sync_group(SyncLds &L, int grp, const uint8_t *_
         cur0 = b & 1;
         nrow = R + nd - d0;
     }
+    // every bit of the widest row the host admits (2 smax <= LMAC_MAXBITS + 4): words_all holds
+    // LMAC_MAXBITS + 128 bits, the last extraction (s + 500, 32 bits on) ends 22 bits past the scan's
     int nbits = 2 * nrow;
-    if (nbits > LMAC_MAXBITS) nbits = LMAC_MAXBITS;
+    if (nbits > LMAC_MAXBITS + 4) nbits = LMAC_MAXBITS + 4;
     const uint8_t *hp = hard + (size_t)ch * smax + d0;
     const int lim = smax - d0;   // the row's symbols from hp
     // pack hard bits with ballots: a word holds 32 dibit symbols (bit 2i = b1, 2i+1 = b2), so lane j
