@@ -53,6 +53,8 @@ def _compare(k, got_demod, got_frames, want, C):
         assert np.array_equal(sym[ch, :n], w["symbols"]), case
         assert np.array_equal(hard[ch, :max(n - 1, 0)], w["hard"]), case
         assert np.array_equal(soft[ch, :2 * max(n - 1, 0)], w["soft"]), case
+        if got_frames is None:   # the demod alone
+            continue
         got = got_frames[ch]
         assert [(f["position"], f["burst_kind"]) for f in got] == [(p, kd) for p, kd, _ in w["bursts"]], case
         for f, (_, _, dec) in zip(got, w["bursts"]):
@@ -76,6 +78,61 @@ def test_stream_bit_identical_to_oracle(sizes, acquire):
         _compare(k, d, frames, want[k], C)
         if acquire:
             assert [int(v) for v in lm.cell_state] == [want[k][ch]["cell"] for ch in range(C)], k
+    assert (np.asarray(st.track["acquired"]) == 1).all()
+
+
+def _profile_stages(c):
+    """The stage names the context's profile recorded since the previous read."""
+    names = ctypes.create_string_buffer(4096)
+    ms, cnt, n = (ctypes.c_double * 64)(), (ctypes.c_int64 * 64)(), ctypes.c_int()
+    c.check(c.lib.tetra_profile_read(c.handle, names, 4096, ms, cnt, 64, ctypes.byref(n)), "tetra_profile_read")
+    return {s.decode() for s in names.raw.split(b"\0")[:n.value]}
+
+
+_DEMOD_STAGES = {"etsi_demod", "etsi_chanfilt", "etsi_timing"}
+_LAUNCHES = {"skip": set(), "fused": {"etsi_demod"}, "pair": {"etsi_chanfilt", "etsi_timing"}}
+
+
+@pytest.mark.parametrize("fmt", ["cf32", "sc16"])
+@pytest.mark.parametrize("sizes,paths", [
+    ([40, 50002, 50000, 3000], ["skip", "fused", "fused", "fused"]),
+    ([134410, 134408], ["pair", "pair"]),
+    ([131072, 131072], ["fused", "fused"]),
+])
+def test_stream_every_demod_path_vs_oracle(sizes, paths, fmt):
+    """Every launch path of tetra_demod_etsi_stream, chunk by chunk against the oracle stream (nsym,
+    symbols, hard dibits and soft bits bit-identical; SC16 against the oracle on its 1/32768-scaled
+    samples), and the path each chunk took from the profile's stage names:
+    [40, ...]: a first window shorter than the filter (M2 <= 0: k_track_skip, nsym = 0, no demod
+    stage), then windows of W = 2 (mod 4) samples -- SC16 leaves the per-wave kernel for
+    k_chanfilt<uint2> fused with a carried track, cf32 stays per-wave;
+    [134410, 134408]: M2 = 4000 > YLDS in the first window and more in the second -- the unfused
+    k_chanfilt + k_timing pair with track, yoff > 0 and an acquired loop (SC16 rows not a multiple
+    of four samples);
+    [131072, 131072]: the per-wave fused kernel for both formats."""
+    from tetraear import _hip
+    from tetraear.signal.etsi import EtsiStream, synth
+    C, total = 2, sum(sizes)
+    iq = synth(C, total, seed=67, snr_db=18.0, cfo_max=600.0)[0]
+    inp = iq
+    if fmt == "sc16":
+        inp = np.stack([np.round(iq.real * 32768), np.round(iq.imag * 32768)], -1).clip(-32768, 32767).astype(np.int16)
+        iq = (inp[..., 0].astype(np.float32) / 32768 + 1j * (inp[..., 1].astype(np.float32) / 32768)).astype(np.complex64)
+    plan = _chunk_plan(total, sizes)
+    assert [n for _, n in plan] == sizes
+    want = _oracle_chunks(iq, 2.4e6, plan)
+    st, c = EtsiStream(2.4e6, C), _hip.ctx()
+    c.check(c.lib.tetra_profile(c.handle, 1), "tetra_profile")
+    try:
+        _profile_stages(c)   # drop earlier records
+        for k, (at, n) in enumerate(plan):
+            d = st.demod(inp[:, at:at + n])
+            assert _profile_stages(c) & _DEMOD_STAGES == _LAUNCHES[paths[k]], (k, paths[k])
+            if paths[k] == "skip":
+                assert not d[3].any()
+            _compare(k, d, None, want[k], C)
+    finally:
+        c.check(c.lib.tetra_profile(c.handle, 0), "tetra_profile")
     assert (np.asarray(st.track["acquired"]) == 1).all()
 
 

@@ -3,7 +3,7 @@
 # DESIGN.md (records: profiles/r0*_ab_*.txt).  Boxes differ by up to +-5 %, so variants are only ever
 # compared inside one gpurun call, three rounds interleaved.
 #
-#   tools/ab.sh build NAME SPEC [SRC]   lib/variants/libNAME.so, csrc/SRC.hip (default etsi_rx) changed by
+#   tools/ab.sh build NAME SPEC [SRC]   lib/variants/libNAME.so, csrc/SRC.hip (default etsi_demod) changed by
 #        SPEC = tools/ab_patches/X.py   a python filter (stdin -> stdout; timing-only patches: a phase
 #                                       skipped, outputs wrong -- never #ifdefs in the product kernels)
 #             | tools/ab_patches/X.sed  a sed script
@@ -24,7 +24,7 @@ summ() {   # one line per run: label, ms/step, per-stage ms, read floor
 }
 case $cmd in
 build)
-    NAME=$1; SPEC=$2; SRC=${3:-etsi_rx}
+    NAME=$1; SPEC=$2; SRC=${3:-etsi_demod}
     cd $R/tetraear-bladerf_amd
     make -s
     mkdir -p build/var lib/variants
@@ -42,7 +42,8 @@ build)
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wall -Wno-unused-function \
         $FLAGS -c $IN -o build/var/${SRC}_$NAME.o
     /opt/rocm/bin/hipcc -shared --offload-arch=gfx950 -o lib/variants/lib$NAME.so \
-        $(ls build/*.o | grep -v "/$SRC.o") build/var/${SRC}_$NAME.o -L/opt/rocm/lib -lrocfft -Wl,-rpath,/opt/rocm/lib
+        $(for f in csrc/*.hip; do b=$(basename $f .hip); [ $b = $SRC ] || echo build/$b.o; done) \
+        build/var/${SRC}_$NAME.o -L/opt/rocm/lib -lrocfft -Wl,-rpath,/opt/rocm/lib
     echo tetraear-bladerf_amd/lib/variants/lib$NAME.so ;;
 run)
     O=$R/gpurun_out/ab; mkdir -p $O; cd $R
