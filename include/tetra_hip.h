@@ -367,7 +367,16 @@ int tetra_etsi_timing_om(tetra_ctx *ctx, const tetra_etsi_plan *plan, const void
 int tetra_etsi_timing_chunks(tetra_ctx *ctx, const tetra_etsi_plan *plan, const void *y, size_t M, size_t rowlen,
                              size_t nchunk, size_t stride, size_t len, const void *om, size_t ngrp, int U, void *soft,
                              int8_t *softbits, uint8_t *hard, int32_t *nsym, size_t smax, float *diag);
-/* Fused demod (chanfilt + timing) over a batch. */
+/* Fused demod (chanfilt + timing) over a batch.
+ *   Amplitude range (cf32 is taken as it comes, not assumed to lie in +-1): for a nominal row
+ *   (amplitude about 0.5) scaled by 2^k, every output is scale-exact -- the same dibits, soft bits,
+ *   nsym and diag, the symbols times 2^k, bit for bit -- for k in [-16, +10] (amplitude 8e-6 ... 500;
+ *   SC16 at a few LSB is inside).  Above it the CFO correction is off (the 4th-power sums overflow:
+ *   the rotation is the identity, dibits stay right while the offset is small); from about 2^29 the
+ *   soft bits read 0, from about 2^58 nsym is 0 and diag[0] NaN.  Below it the rotation decays to
+ *   the identity (2^-19 ... 2^-40), then the soft bits read 0, and under about 2^-100 the row
+ *   decodes as silence.  No amplitude returns wrong dibits with symbols present.  DESIGN.md §5.15.
+ *   A row of fewer than 16 filter outputs has nsym 0 and diag zeros. */
 int tetra_demod_etsi(tetra_ctx *ctx, const tetra_etsi_plan *plan, const void *iq, size_t C, size_t N,
                      void *soft, int8_t *softbits, uint8_t *hard, int32_t *nsym, size_t smax, float *diag);
 /* The same two entry points for an explicit input format (TETRA_CF32 or TETRA_SC16); the

@@ -21,6 +21,7 @@
  * receiver design; the functions below define it, and the GPU kernels reproduce the same float
  * operations (explicit fmaf, emulated 64-lane wave reductions), compiled with -ffp-contract=off.
  */
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -263,6 +264,28 @@ static void csqrt_p(float x, float y, float *a, float *b)
     }
 }
 
+/* CFO rotation conj((-Z/|Z|)^(1/4)) of Z = sum d^4.  Z goes with the 8th power of the input
+ * amplitude, so Zr^2 + Zi^2 overflows or underflows long before Z does: Z is first scaled by the
+ * exact power of two that brings max(|Zr|, |Zi|) into [0.5, 1) (frexpf / ldexpf: no rounding, so
+ * wherever the unscaled norm neither overflowed nor underflowed the result has the same bits).
+ * Z = 0, infinite or NaN: no estimate, the identity rotation. */
+static void cfo_rotation(float Zr, float Zi, float *rr, float *ri)
+{
+    *rr = 1.0f;
+    *ri = 0.0f;
+    float m = fmaxf(fabsf(Zr), fabsf(Zi));
+    if (!(m > 0.0f && m <= FLT_MAX)) return;
+    int e;
+    (void)frexpf(m, &e);
+    float zr = ldexpf(Zr, -e), zi = ldexpf(Zi, -e);
+    float zm = sqrtf(fmaf(zr, zr, zi * zi));
+    float vr, vi, wr, wi;
+    csqrt_p(-zr / zm, -zi / zm, &vr, &vi);
+    csqrt_p(vr, vi, &wr, &wi);
+    *rr = wr;
+    *ri = -wi;
+}
+
 /* Timing recovery + differential decision over y (4 samples/symbol, M2 samples).
  *   Oerder-Meyr feed-forward timing phase, then block Gardner tracking (64 symbols per block).
  *   soft_sym [smax] cf32 symbol-spaced samples; softbits [2*smax] int8; hard [smax] dibit symbols.
@@ -453,15 +476,8 @@ static int timing_core(const float *y, int M2, const float *om, int yoff, eo_tra
         am[l] += sqrtf(fmaf(dr, dr, di * di));
     }
     float Zr = wave_sum(zr), Zi = wave_sum(zi), A = wave_sum(am);
-    float rr = 1.0f, ri = 0.0f;
-    float zm = sqrtf(fmaf(Zr, Zr, Zi * Zi));
-    if (zm > 0.0f) {
-        float ur = -Zr / zm, ui = -Zi / zm, vr, vi, wr, wi;
-        csqrt_p(ur, ui, &vr, &vi);
-        csqrt_p(vr, vi, &wr, &wi);
-        rr = wr;
-        ri = -wi;
-    }
+    float rr, ri;
+    cfo_rotation(Zr, Zi, &rr, &ri);
     float sc = 0.0f;
     if (S > 1 && A > 0.0f) sc = soft_scale / (A / (float)(S - 1));
     for (int j = 1; j < S; ++j) {

@@ -24,6 +24,7 @@
 //                cubic interpolation, differential decision, 4th-power CFO estimate, int8 soft bits.
 //   k_track_skip a streaming window too short for the filter: the carried loops' positions move on.
 //   k_etsi_decide  the differential decision alone, on given symbol-spaced samples.
+#include <cfloat>
 #include <cstdlib>
 
 #include "common.h"
@@ -160,6 +161,25 @@ __device__ __forceinline__ float2 csqrt_p(float x, float y) {
     float s = sqrtf((r - x) * 0.5f);
     if (y < 0.0f) s = -s;
     return make_float2(y / (2.0f * s), s);
+}
+
+// CFO rotation conj((-Z/|Z|)^(1/4)) of Z = sum d^4 (oracle cfo_rotation).  Z goes with the 8th power
+// of the input amplitude, so Zr^2 + Zi^2 overflows or underflows long before Z does: Z is first scaled
+// by the exact power of two that brings max(|Zr|, |Zi|) into [0.5, 1) (v_frexp_exp / v_ldexp: no
+// rounding).  Z = 0, infinite or NaN: no estimate, the identity rotation.  Once per channel.
+__device__ __forceinline__ void cfo_rotation(float Zr, float Zi, float &rr, float &ri) {
+    rr = 1.0f;
+    ri = 0.0f;
+    const float m = fmaxf(fabsf(Zr), fabsf(Zi));
+    if (!(m > 0.0f && m <= FLT_MAX)) return;
+    int e;
+    (void)frexpf(m, &e);
+    const float zr = ldexpf(Zr, -e), zi = ldexpf(Zi, -e);
+    const float zm = sqrtf(fmaf(zr, zr, zi * zi));
+    const float2 v = csqrt_p(-zr / zm, -zi / zm);
+    const float2 w = csqrt_p(v.x, v.y);
+    rr = w.x;
+    ri = -w.y;
 }
 
 // The timing + decision stage for one channel.  timing_track runs on one wave (lane = 0..63): the
@@ -455,14 +475,8 @@ __device__ __forceinline__ TrackOut timing_track(const float2 *y, int M2, float 
     if constexpr (SPLIT) return o;   // rr, ri, sc: cfo_consumer's
     // CFO rotation conj((-Z/|Z|)^(1/4)) and the soft scale from the mean |d|
     const float Zr = wave_sum(zr), Zi = wave_sum(zi), A = wave_sum(am);
-    float rr = 1.0f, ri = 0.0f;
-    const float zm = sqrtf(fmaf(Zr, Zr, Zi * Zi));
-    if (zm > 0.0f) {
-        const float2 v = csqrt_p(-Zr / zm, -Zi / zm);
-        const float2 w = csqrt_p(v.x, v.y);
-        rr = w.x;
-        ri = -w.y;
-    }
+    float rr, ri;
+    cfo_rotation(Zr, Zi, rr, ri);
     o.rr = rr;
     o.ri = ri;
     o.sc = (S > 1 && A > 0.0f) ? soft_scale / (A / (float)(S - 1)) : 0.0f;
@@ -498,14 +512,8 @@ __device__ __forceinline__ void cfo_consumer(const float2 *dp, float soft_scale,
         __builtin_amdgcn_s_sleep(1);
     }
     const float Zr = wave_sum(zr), Zi = wave_sum(zi), A = wave_sum(am);
-    float rr = 1.0f, ri = 0.0f;
-    const float zm = sqrtf(fmaf(Zr, Zr, Zi * Zi));
-    if (zm > 0.0f) {
-        const float2 v = csqrt_p(-Zr / zm, -Zi / zm);
-        const float2 w = csqrt_p(v.x, v.y);
-        rr = w.x;
-        ri = -w.y;
-    }
+    float rr, ri;
+    cfo_rotation(Zr, Zi, rr, ri);
     if (lane == 0) {
         o->rr = rr;
         o->ri = ri;
@@ -588,8 +596,8 @@ __device__ __forceinline__ void timing_wave(const float2 *y, int M2, float gain,
         if (clk) {
             __builtin_amdgcn_s_waitcnt(0);   // the decision pass's stores issued and done
             clk[3] = (uint32_t)wall_clock64();
-        } else if (diag_ch && M2 >= 16) {
-            *diag_ch = make_float4(o.base, o.delta, o.rr, o.ri);
+        } else if (diag_ch) {   // fewer than 16 samples: no timing ran, zeros (not what the buffer held)
+            *diag_ch = M2 >= 16 ? make_float4(o.base, o.delta, o.rr, o.ri) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
 }
@@ -830,7 +838,8 @@ __device__ __forceinline__ void timing_tail(const float2 *ly, float2 *scr, const
     }
     __syncthreads();
     const TrackOut o = *tro;
-    if (tid == 0 && to.diag && M2 >= 16 && !probe) to.diag[ch] = make_float4(o.base, o.delta, o.rr, o.ri);
+    if (tid == 0 && to.diag && !probe)   // fewer than 16 samples: no timing ran, zeros (not what the buffer held)
+        to.diag[ch] = M2 >= 16 ? make_float4(o.base, o.delta, o.rr, o.ri) : make_float4(0.f, 0.f, 0.f, 0.f);
     auto stamp = [&]() {
         if (probe && tid == 0) {
             __builtin_amdgcn_s_waitcnt(0);
