@@ -470,6 +470,90 @@ int tetra_lmac_etsi_stream(tetra_ctx *ctx, const int8_t *softbits, const uint8_t
                            uint32_t *cell_init, int32_t *nburst, int32_t *bursts, int32_t *nblock, int32_t *blocks,
                            uint8_t *type1);
 
+/* ---------------------------------------------------------------- TDMA timebase + MAC PDU headers
+ * What a receiver reads next from the lower MAC's outputs, on the device: per burst the TDMA
+ * timeslot / frame / multiframe, per CRC-good block the headers of its MAC PDUs, as small int32
+ * records (k_etsi_mac, one launch).  Stands in for the header dissection of the reference's
+ * TetraProtocolParser.parse_mac_pdu (/root/reference/tetraear/core/protocol.py:349-596) on
+ * channel-decoded SCH/F, SCH/HD and BSCH type-1 blocks, whose layout (EN 300 392-2 §21.4) that
+ * parser's raw-frame layout does not fit; tetra_mac_headers above keeps the reference's own layout
+ * for the compat chain.  The SYNC PDU and the TDMA timebase have no reference counterpart.  The
+ * field layouts are transcribed from EN 300 392-2 §21.4 / §18.4.2 and not pinned against a
+ * conformance vector; the records carry raw fields.
+ *
+ * Inputs: the outputs of tetra_lmac_etsi / _acquire / _stream (host or device) and that call's
+ * nsym.  Nothing past nburst[c] / nblock[c] (clamped to MAXB / MAXJ) or past a block's type-1
+ * length is read.  A type-1 bit is byte & 1, bit 0 the block's first, fields MSB first.
+ *
+ * pdus [C][MAXJ][MAXPDU][16]: the walk of a CRC-good block of n1 bits.  BSCH: one SYNC record.
+ * SCH: from off = 0, while n1 - off >= 16, parse and count the PDU at off; stop after a null PDU,
+ * FRAG, a broadcast or supplementary PDU, L = 62 / 63 or STATUS 1, else off += 8 L.  npdu [C][MAXJ]
+ * (fully written) counts them, 0 for a CRC-bad block and for j >= nblock[c]; the first MAXPDU are
+ * recorded, records past the count are not written.  Length indication L: 2..34 octets (8 L may run
+ * past the block end by fewer than 8 bits: cut there), 62 / 63 the rest of the block, else malformed.
+ *
+ * slots [C][MAXB][TETRA_SLOT_FIELDS] (rows past nburst[c] not written) and tdma [C] (in/out): the
+ * timebase, bursts in order, p = bit0 + start bit (int64):
+ *   1. an SB whose BSCH block is CRC-good with a STATUS 0 SYNC record: slot from its TN/FN/MN,
+ *      FLAGS bit 0 (bit 1: the channel was locked and rule 2 gave another slot or none); anchor =
+ *      (p, slot), locked;
+ *   2. else when locked: d = p - anchor_bit, k = (d + 255) / 510, r = d - 510 k; d < 0 or
+ *      k >= TETRA_TDMA_EXPIRE drops the lock (rule 3); |r| <= TETRA_TDMA_TOL: slot = (anchor_slot
+ *      + k) % TETRA_TDMA_SLOTS and the anchor moves to (p, slot); else unknown, anchor kept;
+ *   3. unlocked or unknown: the row reads 0, 0, 0, 0.
+ * After the last burst bit0 += 2 max(nsym[c] - 1, 0).
+ * With device pointers the call enqueues on the context stream and returns without waiting. */
+#define TETRA_ETSI_MAXPDU 4
+#define TETRA_TDMA_SLOTS 4320          /* 60 multiframes x 18 frames x 4 slots */
+#define TETRA_TDMA_TOL 4               /* bits a burst may sit off the slot grid */
+#define TETRA_TDMA_EXPIRE 72           /* slots without a burst after which the timebase is dropped */
+typedef struct tetra_etsi_tdma {       /* per channel, carried from chunk to chunk; all zero = new stream */
+    int64_t bit0;                      /* stream bit index of this chunk's first new dibit */
+    int64_t anchor_bit;                /* stream bit of the last burst placed on the slot grid */
+    int32_t anchor_slot;               /* its slot count ((MN-1)*18 + (FN-1))*4 + TN field, 0..4319 */
+    int32_t locked;
+} tetra_etsi_tdma;
+enum { TETRA_SLOT_TN = 0, TETRA_SLOT_FN, TETRA_SLOT_MN, TETRA_SLOT_FLAGS, TETRA_SLOT_FIELDS = 4 };
+/* TN 1..4, FN 1..18, MN 1..60, all 0 = unknown.
+ * FLAGS bit 0: set from this burst's own SYNC PDU; bit 1: that PDU disagreed with the prediction */
+/* PDU record fields common to every kind */
+enum {
+    TETRA_PDU_KIND = 0,     /* TETRA_PDU_* below */
+    TETRA_PDU_OFFSET,       /* first bit of the PDU in the block */
+    TETRA_PDU_NBITS,        /* bits the PDU occupies */
+    TETRA_PDU_STATUS,       /* 0 ok; 1 malformed or truncated: a bad L, a header or SYSINFO body past the PDU
+                               or block end, a SYNC with FN outside 1..18 or MN outside 1..60 */
+    /* RESOURCE, FRAG, END, null (a field a kind does not have reads 0; SSI and AUX read -1) */
+    TETRA_PDU_FILL = 4,     /* fill-bit indication */
+    TETRA_PDU_ENC,          /* encryption mode */
+    TETRA_PDU_LENGTH,       /* raw L */
+    TETRA_PDU_ADDR_TYPE,    /* 0 null, 1 SSI, 2 event label, 3 USSI, 4 SMI, 5 SSI + event label,
+                               6 SSI + usage marker, 7 SMI + event label */
+    TETRA_PDU_SSI,          /* the 24-bit SSI, USSI or SMI */
+    TETRA_PDU_AUX,          /* event label (10 bits) or usage marker (6) */
+    TETRA_PDU_HDR_BITS,     /* bit within the PDU after the parsed header (where the optional
+                               elements begin): RESOURCE 16 + address, END 11, FRAG 4 */
+    TETRA_PDU_FLAGS,        /* bit 0 position of grant, bit 1 random access flag */
+    TETRA_PDU_FIELDS = 16
+    /* SYNC 4..15: system code, colour code, TN field, FN, MN, sharing mode, TS reserved frames, flags
+     *   (bit 0 U-plane DTX, bit 1 frame-18 extension, bit 2 late entry), MCC, MNC, neighbour cell
+     *   broadcast, cell service level.
+     * SYSINFO 4..15: main carrier, band, offset, duplex spacing, reverse operation, number of common
+     *   secondary control channels, MS_TXPWR_MAX_CELL, RXLEV_ACCESS_MIN, ACCESS_PARAMETER |
+     *   RADIO_DOWNLINK_TIMEOUT << 4 | optional field flag << 8, hyperframe/CCK flag << 16 | its 16-bit
+     *   value, location area, subscriber class | BS service details << 16 (a SYSINFO whose 124 bits
+     *   do not fit the block: STATUS 1, fields 0).
+     * ACCESS-DEFINE, other broadcast, supplementary: 4..15 read 0. */
+};
+enum {
+    TETRA_PDU_RESOURCE = 0, TETRA_PDU_FRAG, TETRA_PDU_END, TETRA_PDU_SYSINFO, TETRA_PDU_ACCESS_DEFINE,
+    TETRA_PDU_BROADCAST, TETRA_PDU_SUPPL, TETRA_PDU_SYNC, TETRA_PDU_NULL
+};
+int tetra_etsi_mac(tetra_ctx *ctx, const int32_t *nsym, size_t C, const int32_t *nburst, const int32_t *bursts,
+                   const int32_t *nblock, const int32_t *blocks, const uint8_t *type1, tetra_etsi_tdma *tdma,
+                   int32_t *slots /*[C][MAXB][4]*/, int32_t *npdu /*[C][MAXJ]*/,
+                   int32_t *pdus /*[C][MAXJ][MAXPDU][16]*/);
+
 /* The ETSI receiver's AFC mixer on a streaming window: out [C][N] cf32 = iq (cf32 rows ld samples
  * apart) x exp(-j 2 pi f (n0 + n) / fs), n0 = the window's first sample in the capture (frequency_shift's
  * float64 arithmetic, processor.py:85-100, with one continuous phase across windows); mix_c [C] as

@@ -69,6 +69,16 @@ ETSI_RESERVE, ETSI_MARGIN = 256, 8   # streaming rows: dibits ahead of a chunk's
 # struct tetra_etsi_track (include/tetra_hip.h): one channel's carried timing loop
 ETSI_TRACK = __import__("numpy").dtype([("base", "<f4"), ("delta", "<f4"), ("prev_re", "<f4"), ("prev_im", "<f4"),
                                        ("acquired", "<i4"), ("reserved", "<i4", (3,))])
+# tetra_etsi_mac (include/tetra_hip.h): struct tetra_etsi_tdma, the slot rows and the PDU records
+ETSI_MAXPDU, PDU_FIELDS = 4, 16
+TDMA_SLOTS, TDMA_TOL, TDMA_EXPIRE = 4320, 4, 72
+ETSI_TDMA = __import__("numpy").dtype([("bit0", "<i8"), ("anchor_bit", "<i8"), ("anchor_slot", "<i4"),
+                                      ("locked", "<i4")])
+SLOT_TN, SLOT_FN, SLOT_MN, SLOT_FLAGS, SLOT_FIELDS = range(5)
+(PDU_KIND, PDU_OFFSET, PDU_NBITS, PDU_STATUS, PDU_FILL, PDU_ENC, PDU_LENGTH, PDU_ADDR_TYPE, PDU_SSI, PDU_AUX,
+ PDU_HDR_BITS, PDU_FLAGS) = range(12)
+(PDU_RESOURCE, PDU_FRAG, PDU_END, PDU_SYSINFO, PDU_ACCESS_DEFINE, PDU_BROADCAST, PDU_SUPPL, PDU_SYNC,
+ PDU_NULL) = range(9)
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -135,6 +145,7 @@ def _bind(L):
         "tetra_demod_etsi_stream": (_i32, [_vp, ctypes.POINTER(EtsiPlan), _vp, _i32, _sz, _sz, _sz, ctypes.c_int,
                                            _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]),
         "tetra_lmac_etsi_stream": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "tetra_etsi_mac": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "tetra_etsi_mix": (_i32, [_vp, _vp, _sz, _sz, _sz, _vp, ctypes.c_double, ctypes.c_int64, _vp]),
         "tetra_etsi_decode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
         "tetra_etsi_encode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp]),

@@ -88,7 +88,7 @@ def _bits_u8(bits):
 class TetraDecoder:
     """Decodes TETRA frames from demodulated symbols (decoder.py:16)."""
 
-    def __init__(self, key_manager=None, auto_decrypt: bool = True, mode=None):
+    def __init__(self, key_manager=None, auto_decrypt: bool = True, mode=None, mac: bool = False):
         self.SYNC_PATTERN = [0, 1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0,
                              1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0]
         self.FRAME_LENGTH = 510
@@ -100,6 +100,7 @@ class TetraDecoder:
         from tetraear.signal.processor import demod_mode
         self.mode = demod_mode(mode)
         self._etsi = None
+        self.etsi_mac = bool(mac)   # mode="etsi": TDMA timebase + MAC PDU headers on the frames (EtsiLowerMac(mac=True))
 
     # ------------------------------------------------------------------ keys and the reference's rest
     def set_keys(self, keys):
@@ -393,6 +394,7 @@ class TetraDecoder:
             crc_ok = bool(f["crc_ok"])
             self.protocol_parser.count_burst(crc_ok)
             frame.update(burst_crc=crc_ok, blocks=f["blocks"], burst=f["burst"], burst_kind=f["burst_kind"])
+            frame.update({k: f[k] for k in ("tn", "fn", "mn", "slot_flags") if k in f})   # EtsiLowerMac(mac=True)
             while k < len(owner) and owner[k] == i:   # the MAC state advances in block order
                 pdu = self.protocol_parser.mac_state(fields[k], data[k])
                 if pdu is not None:
@@ -413,5 +415,5 @@ class TetraDecoder:
     def _etsi_rx(self):
         if self._etsi is None:
             from tetraear.core.etsi import EtsiLowerMac
-            self._etsi = EtsiLowerMac()
+            self._etsi = EtsiLowerMac(mac=self.etsi_mac)
         return self._etsi

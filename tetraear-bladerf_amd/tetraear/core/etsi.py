@@ -7,6 +7,8 @@ This module decodes what the north star asks for (EN 300 392-2 §8.2, §9.4.4):
                                     training sequence p -> two SCH/HD blocks (216 -> 124 bits)
   synchronisation burst -> BSCH (120 -> 60 bits, colour code 0) + SCH/HD on block 2
 The work runs in tetra_lmac_etsi (k_lmac_etsi); this module packages results as frame dicts.
+With ``mac=True`` tetra_etsi_mac (k_etsi_mac) follows it on the device: the TDMA timeslot / frame /
+multiframe of every burst and the MAC PDU headers of every CRC-good block (EN 300 392-2 §21.4).
 """
 import numpy as np
 
@@ -28,6 +30,40 @@ def cell_of(init):
     return (ecc >> 20) & 0x3FF, (ecc >> 6) & 0x3FFF, ecc & 0x3F
 
 
+PDU_NAMES = ("RESOURCE", "FRAG", "END", "SYSINFO", "ACCESS-DEFINE", "BROADCAST", "SUPPLEMENTARY", "SYNC", "NULL")
+SYSINFO_OFFSET_HZ = {0: 0, 1: 6250, 2: -6250, 3: 12500}
+
+
+def pdu_dict(rec):
+    """One tetra_etsi_mac PDU record (16 int32, include/tetra_hip.h) as a dict with named fields."""
+    r = [int(v) for v in rec]
+    d = {"kind": PDU_NAMES[r[_hip.PDU_KIND]], "offset": r[_hip.PDU_OFFSET], "nbits": r[_hip.PDU_NBITS],
+         "ok": r[_hip.PDU_STATUS] == 0}
+    k = r[_hip.PDU_KIND]
+    if k in (_hip.PDU_RESOURCE, _hip.PDU_FRAG, _hip.PDU_END, _hip.PDU_NULL):
+        d.update(fill=r[_hip.PDU_FILL], header_bits=r[_hip.PDU_HDR_BITS])
+        if k != _hip.PDU_FRAG:
+            d.update(length=r[_hip.PDU_LENGTH], grant=r[_hip.PDU_FLAGS] & 1)
+        if k in (_hip.PDU_RESOURCE, _hip.PDU_NULL):
+            d.update(encryption_mode=r[_hip.PDU_ENC], address_type=r[_hip.PDU_ADDR_TYPE],
+                     random_access=(r[_hip.PDU_FLAGS] >> 1) & 1,
+                     ssi=None if r[_hip.PDU_SSI] < 0 else r[_hip.PDU_SSI],
+                     aux=None if r[_hip.PDU_AUX] < 0 else r[_hip.PDU_AUX])
+    elif k == _hip.PDU_SYNC:
+        d.update(system_code=r[4], colour_code=r[5], tn=r[6], fn=r[7], mn=r[8], sharing_mode=r[9],
+                 ts_reserved_frames=r[10], dtx=r[11] & 1, frame18_extension=(r[11] >> 1) & 1,
+                 late_entry=(r[11] >> 2) & 1, mcc=r[12], mnc=r[13], neighbour_cell_broadcast=r[14],
+                 cell_service_level=r[15])
+    elif k == _hip.PDU_SYSINFO and d["ok"]:
+        d.update(main_carrier=r[4], band=r[5], carrier_offset=r[6], duplex_spacing=r[7], reverse_operation=r[8],
+                 num_cscch=r[9], ms_txpwr_max_cell=r[10], rxlev_access_min=r[11], access_parameter=r[12] & 15,
+                 radio_downlink_timeout=(r[12] >> 4) & 15, optional_field_flag=(r[12] >> 8) & 3,
+                 hyperframe_cck_flag=(r[13] >> 16) & 1, hyperframe_or_cck=r[13] & 0xFFFF, location_area=r[14],
+                 subscriber_class=r[15] & 0xFFFF, bs_service_details=(r[15] >> 16) & 0xFFF,
+                 downlink_hz=r[5] * 100e6 + r[4] * 25e3 + SYSINFO_OFFSET_HZ[r[6]])
+    return d
+
+
 UNKNOWN_CELL = scrambling_init(0, 0, 0)   # colour code 0: what a receiver descrambles with before the BSCH
 
 
@@ -47,9 +83,16 @@ class EtsiLowerMac:
     channel's MCC / MNC / colour code (tetra_lmac_etsi_acquire).  The acquired cell persists across
     calls per channel -- the state the reference parser keeps from a SYSINFO broadcast
     (/root/reference/tetraear/core/protocol.py:479-485) -- and is exposed as ``cells`` /
-    ``mcc`` / ``mnc`` / ``colour_code``."""
+    ``mcc`` / ``mnc`` / ``colour_code``.
 
-    def __init__(self, mcc=None, mnc=None, colour_code=None):
+    ``mac=True``: tetra_etsi_mac runs after the lower MAC.  Every frame gains ``tn`` / ``fn`` / ``mn``
+    (None while the channel has no timebase) and ``slot_flags``, every block ``pdus`` (dicts of the
+    first TETRA_ETSI_MAXPDU MAC PDU headers, pdu_dict) and ``npdu``.  The timebase is carried from
+    chunk to chunk by decode_stream / decode (reset_stream() drops it) and is fresh for every
+    decode_batch.  Without it the frames are unchanged."""
+
+    def __init__(self, mcc=None, mnc=None, colour_code=None, mac=False):
+        self.mac = bool(mac)
         self.acquire = mcc is None and mnc is None and colour_code is None
         self.cell = None if self.acquire else scrambling_init(mcc or 0, mnc or 0, colour_code or 0)
         self.cell_state = None   # [C] scrambling inits of the acquired cells (acquisition mode)
@@ -61,6 +104,7 @@ class EtsiLowerMac:
     def reset_stream(self):
         """decode_stream / decode start a new capture: no carried dibits."""
         self._rows = None   # (soft rows [C, 2 stride], hard rows [C, stride], lead [C]): the carried tails
+        self._tdma = None   # [C] tetra_etsi_tdma: the carried timebases (mac=True)
 
     @property
     def cells(self):
@@ -115,7 +159,22 @@ class EtsiLowerMac:
             c.check(c.lib.tetra_lmac_etsi(c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(nsym), C, smax,
                                           _hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
                     "tetra_lmac_etsi")
-        return self._frames(C, nb, bursts, nk, blocks, t1)
+        return self._frames(C, nb, bursts, nk, blocks, t1, self._run_mac(c, C, nsym, nb, bursts, nk, blocks, t1, None))
+
+    def _run_mac(self, c, C, nsym, nb, bursts, nk, blocks, t1, tdma):
+        """tetra_etsi_mac on the lower MAC's outputs (mac=True; else None): (slots, npdu, pdus).
+        tdma None: a new stream per channel."""
+        if not self.mac:
+            return None
+        if tdma is None:
+            tdma = np.zeros(C, _hip.ETSI_TDMA)
+        slots = np.zeros((C, _hip.ETSI_MAXB, _hip.SLOT_FIELDS), np.int32)
+        npdu = np.zeros((C, _hip.ETSI_MAXJ), np.int32)
+        pdus = np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.PDU_FIELDS), np.int32)
+        c.check(c.lib.tetra_etsi_mac(c.handle, _hip.ptr(nsym), C, _hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk),
+                                     _hip.ptr(blocks), _hip.ptr(t1), _hip.ptr(tdma), _hip.ptr(slots), _hip.ptr(npdu),
+                                     _hip.ptr(pdus)), "tetra_etsi_mac")
+        return slots, npdu, pdus
 
     def _run_stream(self, c, C, nb, bursts, nk, blocks, t1, cells, stream):
         """tetra_lmac_etsi_stream over stream = (soft rows, hard rows, nsym, stride, lead), with the
@@ -170,10 +229,14 @@ class EtsiLowerMac:
         blocks = np.zeros((C, _hip.ETSI_MAXJ, 4), np.int32)
         t1 = np.zeros((C, _hip.ETSI_MAXJ, 268), np.uint8)
         self._run_stream(_hip.ctx(), C, nb, bursts, nk, blocks, t1, cells, (srow, hrow, nsym, stride, lead))
-        return self._frames(C, nb, bursts, nk, blocks, t1)
+        if self.mac and (self._tdma is None or len(self._tdma) != C):
+            self._tdma = np.zeros(C, _hip.ETSI_TDMA)
+        return self._frames(C, nb, bursts, nk, blocks, t1,
+                            self._run_mac(_hip.ctx(), C, nsym, nb, bursts, nk, blocks, t1, self._tdma))
 
     @staticmethod
-    def _frames(C, nb, bursts, nk, blocks, t1):
+    def _frames(C, nb, bursts, nk, blocks, t1, mac=None):
+        """mac: None, or tetra_etsi_mac's (slots, npdu, pdus) for the same call."""
         out = []
         for ch in range(C):
             frames = []
@@ -186,9 +249,17 @@ class EtsiLowerMac:
                     k = int(blocks[ch, j, 0])
                     blks.append({"channel": BLOCK_NAMES[k], "crc_ok": bool(blocks[ch, j, 1]),
                                  "bits": t1[ch, j, :KIND_N1[k]].copy(), "block": int(blocks[ch, j, 3])})
+                    if mac is not None:
+                        n = int(mac[1][ch, j])
+                        blks[-1].update(npdu=n, pdus=[pdu_dict(r) for r in mac[2][ch, j, :min(n, _hip.ETSI_MAXPDU)]])
                 frames.append({"position": start, "burst": BURST_NAMES[kind], "burst_kind": kind,
                                "timeslot": (start // 510) % 4, "blocks": blks,
                                "crc_ok": all(x["crc_ok"] for x in blks)})
+                if mac is not None:
+                    tn, fn, mn, fl = (int(v) for v in mac[0][ch, b])
+                    known = tn != 0
+                    frames[-1].update(tn=tn if known else None, fn=fn if known else None, mn=mn if known else None,
+                                      slot_flags=fl)
             out.append(frames)
         return out
 
