@@ -134,7 +134,7 @@ def filtfilt(b, a, x):
 
 
 # ----------------------------------------------------------------------------- time-blocked decimate
-# The product's latency-mode decimator (tetraear-bladerf_amd/csrc/compat_demod.hip, k_sosb_*), restated
+# The product's latency-mode decimator (tetraear-bladerf_amd/csrc/compat_decimate.hip, k_sosb_*), restated
 # operation for operation, so the GPU can be checked bit for bit; its distance from the reference's
 # sequential decimate is checked against the reference's own fixtures (tests/test_compat_blocked.py).
 # Not a reference function: the reference only has the sequential scipy.signal.decimate
@@ -143,14 +143,14 @@ SB_B, SB_MAXT, SB_NPOW, SB_MAXC, SB_MAXQ = 256, 1024, 10, 64, 16
 
 
 def blocked_fits(C, N, q):
-    """The shapes tetra_demod_compat decimates time-blocked by default (compat_demod.hip: blocked_fits)."""
+    """The shapes tetra_demod_compat decimates time-blocked by default (compat_sos.h: blocked_fits)."""
     return 1 <= C <= SB_MAXC and 2 <= q <= SB_MAXQ and N > 27 and -(-(N + 54) // SB_B) <= SB_MAXT
 
 
 def blocked_table(coef):
     """Phi^(2^r), r < SB_NPOW (Phi = A^SB_B, A the cascade's one-sample zero-input transition in scipy's
     _sosfilt order), as float64 [SB_NPOW, 8, 8]; every product summed in k order, no FMA -- the
-    host loops of compat_demod.hip: blocked_table."""
+    host loops of compat_decimate.hip: blocked_table."""
     c = [float(v) for v in np.asarray(coef, np.float64).ravel()]
     A = [[0.0] * 8 for _ in range(8)]
     for k in range(8):
@@ -249,7 +249,7 @@ def lf_blocked_fits(C, M, ntaps=5):
 
 def lfilter_table(b, a):
     """Psi^(2^r) (Psi = B^LB_B, B scipy lfilter's one-sample zero-input transition of its 4 DF-II-T
-    states), float64 [SB_NPOW, 4, 4], in compat_demod.hip: lfilter_table's operation order."""
+    states), float64 [SB_NPOW, 4, 4], in compat_filtfilt.hip: lfilter_table's operation order."""
     b = [float(v) for v in b]
     a = [float(v) for v in a]
     K = LB_NS
@@ -311,7 +311,7 @@ def _lf_blocked_pass(bb, aa, zi, c, tab):
 
 
 def filtfilt_blocked(b, a, x):
-    """filtfilt(b, a, x) as the product's latency mode computes it (compat_demod.hip: k_lfb_*)."""
+    """filtfilt(b, a, x) as the product's latency mode computes it (compat_filtfilt.hip: k_lfb_*)."""
     assert a[0] == 1.0
     edge = 3 * max(len(a), len(b))
     if x.shape[0] <= edge:

@@ -1,4 +1,4 @@
-"""The compat chain's time-blocked decimator (latency mode; compat_demod.hip k_sosb_*, oracle/compat.py:
+"""The compat chain's time-blocked decimator (latency mode; compat_decimate.hip k_sosb_*, oracle/compat.py:
 decimate_blocked) against the reference's own fixtures, on the CPU.
 
 The blocked form is not scipy's operation order, so it cannot be bit-exact with the reference; the

@@ -4,6 +4,8 @@ Bar (BASELINE.json north_star): integer outputs bit-exact; soft symbols within 1
 decisions are compared bit-exact outside a tie band of 1e-9 rad around the decision thresholds
 (atan2 differs between libms by an ulp); positions in the band are counted and reported.
 """
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -435,3 +437,108 @@ def test_real_short_mixed_offsets_batch_equals_process(hip, N, fs):
         ho = o.process(x[c], fo[c])
         assert ns[c] == len(p.symbols) == len(o.symbols), c
         assert np.array_equal(hard[c, :max(ns[c] - 1, 0)], h) and np.array_equal(h, ho), (c, fo[c])
+
+
+def _profile_stages(c):
+    """The stage names the context's profile recorded since the previous read."""
+    names = ctypes.create_string_buffer(4096)
+    ms, cnt, n = (ctypes.c_double * 64)(), (ctypes.c_int64 * 64)(), ctypes.c_int()
+    c.check(c.lib.tetra_profile_read(c.handle, names, 4096, ms, cnt, 64, ctypes.byref(n)), "tetra_profile_read")
+    return {s.decode() for s in names.raw.split(b"\0")[:n.value]}
+
+
+def _demod_compat(c, fs, x, fo, decimator):
+    """tetra_demod_compat on the rows of x, straight through the C ABI: (hard, soft, nsym, plan, M),
+    soft in the dtype the library wrote (complex64 when it reports float32 symbols)."""
+    from tetraear import _hip
+    from tetraear.signal.processor import compat_plan, mixer_coefficient
+    C, N = x.shape
+    fmt = _hip.TETRA_CF64 if x.dtype == np.complex128 else _hip.TETRA_CF32
+    plan, M, _ = compat_plan(fs, N, fmt, decimator=decimator)
+    smax = M // plan.sps + 1
+    soft = np.empty((C, smax), np.complex128)
+    hard = np.empty((C, smax), np.uint8)
+    ns = np.zeros(C, np.int32)
+    f32 = ctypes.c_int32(0)
+    mc = np.array([mixer_coefficient(f) if f != 0 else 0.0 for f in fo], np.float64)
+    mo = (np.asarray(fo) != 0).astype(np.uint8)
+    c.check(c.lib.tetra_demod_compat(c.handle, plan, _hip.ptr(x), fmt, C, N, _hip.ptr(mc), _hip.ptr(mo), _hip.ptr(soft),
+                                     _hip.ptr(hard), _hip.ptr(ns), smax, f32), "tetra_demod_compat")
+    if f32.value:
+        soft = soft.reshape(-1).view(np.complex64)[:C * smax].reshape(C, smax)
+    return hard, soft, ns, plan, M
+
+
+_F = 1171.875
+_SOS = {"compat_sos_fwd", "compat_sos_bwd"}
+_LF = {"compat_filtfilt_fwd", "compat_filtfilt_bwd"}
+_BLK = {"compat_sosb_fwd", "compat_sosb_bwd", "compat_lfb_fwd", "compat_lfb_bwd"}
+_TL = {"compat_tiled_fwd", "compat_tiled_bwd"}
+_SYM = {"compat_extract", "compat_demod"}
+# id: (fs, dtype, C, N, freq offsets, decimator, stages recorded, soft dtype)
+_PATHS = {
+    "1-banked-q10-premix": (2.4e6, np.complex64, 3, 4001, [_F, -2 * _F, 3 * _F], "sequential",
+                            _SOS | {"compat_mix"} | _LF | _SYM, np.complex128),
+    "2-banked-q10-mixer-inside": (2.4e6, np.complex64, 3, 4001, [_F, 0.0, 3 * _F], "sequential", _SOS | _LF | _SYM,
+                                  np.complex128),
+    "3-batch65-q7": (1.8e6, np.complex64, 65, 3001, list((np.arange(65) % 5 - 2) * _F), "sequential",
+                     _SOS | _LF | _SYM, np.complex128),
+    "4-generic-q4": (1.0e6, np.complex64, 2, 4001, [0.0, _F], "sequential", _SOS | _LF | _SYM, np.complex128),
+    "5-cf64-q10": (2.4e6, np.complex128, 2, 4001, [0.0, _F], "sequential", _SOS | _LF | _SYM, np.complex128),
+    "5-cf64-q7": (1.8e6, np.complex128, 2, 4001, [0.0, _F], "sequential", _SOS | _LF | _SYM, np.complex128),
+    "5-cf64-q4": (1.0e6, np.complex128, 2, 4001, [0.0, _F], "sequential", _SOS | _LF | _SYM, np.complex128),
+    "6-q1-long": (240000.0, np.complex64, 1, 60000, [0.0], "sequential", _LF | _SYM, np.complex128),
+    "7-short-mixed": (2.4e6, np.complex64, 2, 100, [_F, -_F], "sequential", _SOS | _SYM, np.complex128),
+    "7-short-unmixed": (2.4e6, np.complex64, 2, 100, [0.0, 0.0], "sequential", _SOS | _SYM, np.complex64),
+    "8-blocked-cf32": (2.4e6, np.complex64, 2, 4001, [0.0, _F], "blocked", _BLK | _SYM, np.complex128),
+    "8-blocked-cf64": (2.4e6, np.complex128, 2, 4001, [0.0, _F], "blocked", _BLK | _SYM, np.complex128),
+    "9-tiled": (2.4e6, np.complex64, 2, 20001, [0.0, _F], "tiled", _TL | _LF | _SYM, np.complex128),
+    "10-tiled-fallback": (2.4e6, np.complex64, 2, 4001, [0.0, _F], "tiled", _SOS | _LF | _SYM, np.complex128),
+}
+
+
+@pytest.mark.parametrize("case", list(_PATHS))
+def test_every_compat_launch_path_vs_oracle(hip, case):
+    """Every launch path of tetra_demod_compat's host code, channel by channel against the oracle of
+    the same form ("tiled" against the sequential one: it is exact) -- equal nsym, soft symbols
+    within SOFT_TOL, hard decisions equal outside the tie band -- and the path taken, from the set of
+    compat_* stage names the profile recorded for the call.  Rows of a few thousand samples; N odd, so
+    row starts are only 8-byte aligned.
+    1: complex64 at 2.4 MSps, every row mixed: k_sos_fwd_bank, k_sos_bwd_bank<10>, k_mix under
+       "compat_mix" (premix), k_lf_fwd<double, 5, false, 4> / k_lf_bwd<5, 4> (lane quad, no mixer),
+       k_cabs2 + k_extract_lat, k_demod<double, 1024>;
+    2: one row unmixed: no "compat_mix", the mixer inside k_lf_fwd<float, 5, true, 4>;
+    3: 65 rows at 1.8 MSps: k_sos_bwd_bank<7>, one-lane k_lf_fwd<float, 5, true, 1> / k_lf_bwd<5, 1>,
+       k_extract without the prepass, k_demod<double, 64>;
+    4: 1.0 MSps (q = 4): the generic k_sos_bwd<float, 0>;
+    5: complex128 at 2.4, 1.8 and 1.0 MSps: k_sos_fwd<double, 1>, k_sos_bwd<double, 10 / 7 / 0>;
+    6: 240 kSps (q = 1), 60000 samples: no decimator stage; more than 3584 symbols per phase, so
+       k_extract over the k_cabs2 prepass instead of k_extract_lat;
+    7: 100 samples, too short for filtfilt: mixed rows through k_mix (outside any stage) to float64
+       symbols, unmixed rows straight to k_extract<float> / k_demod<float> and float32 symbols;
+    8: "blocked", complex64 and complex128: k_sosb_tile / k_sosb_scan, k_lfb_tile / k_lfb_scan;
+    9: "tiled", 20001 samples (more than one tile): k_tl_spec / k_tl_resolve;
+    10: "tiled", 4001 samples (one tile): the sequential kernels, silently."""
+    fs, dtype, C, N, fo, decimator, stages, soft_dtype = _PATHS[case]
+    rng = np.random.default_rng(1000 + list(_PATHS).index(case))
+    x = (0.3 * (rng.standard_normal((C, N)) + 1j * rng.standard_normal((C, N)))).astype(dtype)
+    hip.check(hip.lib.tetra_profile(hip.handle, 1), "tetra_profile")
+    try:
+        _profile_stages(hip)   # drop earlier records
+        hard, soft, ns, plan, M = _demod_compat(hip, fs, x, fo, decimator)
+        got = {s for s in _profile_stages(hip) if s.startswith("compat_")}
+    finally:
+        hip.check(hip.lib.tetra_profile(hip.handle, 0), "tetra_profile")
+    assert got == stages, (case, sorted(got))
+    assert soft.dtype == soft_dtype
+    if case == "6-q1-long":
+        assert M // plan.sps > 3584   # past k_extract_lat: k_extract reads the prepass rows
+    for ch in range(C):
+        o = O.SignalProcessor(fs, decimator="sequential" if decimator == "tiled" else decimator)
+        h = o.process(x[ch], fo[ch])
+        n = int(ns[ch])
+        assert n == len(o.symbols), (case, ch)
+        assert o.symbols.dtype == soft_dtype or n == 0, (case, ch)
+        if n:
+            assert np.max(np.abs(soft[ch, :n] - o.symbols)) <= SOFT_TOL, (case, ch)
+        _hard_equal(hard[ch, :max(n - 1, 0)], h, o.symbols)

@@ -117,7 +117,9 @@ def test_summaries_carry_source_provenance_and_bench_rejects_stale(tmp_path):
     assert src and src["file"] == "etsi_demod.hip" and len(src["sha256"]) == 64
     assert P.kernel_source("k_timing")["file"] == "etsi_demod.hip"
     assert P.kernel_source("k_etsi_viterbi")["file"] == "etsi_lmac.hip"
-    assert P.kernel_source("k_sos_fwd_bank")["file"] == "compat_demod.hip"
+    assert P.kernel_source("k_sos_fwd_bank")["file"] == "compat_decimate.hip"
+    assert P.kernel_source("k_lf_fwd")["file"] == "compat_filtfilt.hip"
+    assert P.kernel_source("k_extract")["file"] == "compat_symbols.hip"
     assert P.kernel_source("no_such_kernel") is None
     launches = [(K16, 500), (K16, 500), (K16, 1000), (K16, 1200)]
     d = _run(str(tmp_path), launches, {K16: (1000.0, 10.0)})

@@ -1,10 +1,9 @@
-// compat_sos.h -- the pieces of the compat decimator (scipy sosfiltfilt, cheby1(8) -> 4 sections) that
-// its sequential kernels (compat_demod.hip) and its time-tiled kernels (compat_tiled.hip) share: the
-// row layouts, the one-section DF-II-T step in scipy's operation order, and the banked lane mapping.
+// compat_sos.h -- what the units of the compat chain share: the row layouts, the time-blocked limits
+// and the stage entry points tetra_demod_compat (compat_demod.hip) strings together; then the pieces
+// of the decimator (sosfiltfilt, 4 sections) common to compat_decimate.hip and compat_tiled.hip: the
+// one-section DF-II-T step in scipy's operation order and the banked lane mapping.
 #pragma once
 #include "common.h"
-
-namespace {
 
 // Strided view of complex rows: element (ch, n) real part at base[off(ch, n)], imag at +1.
 struct Lay {
@@ -13,9 +12,75 @@ struct Lay {
         return (size_t)(ch >> 5) * s_grp + (size_t)n * s_n + (size_t)(ch & 31) * s_lane;
     }
 };
-static Lay row_major(long len) { return Lay{(size_t)64 * len, 2, (size_t)2 * len}; }
-static Lay grouped(long len) { return Lay{(size_t)64 * len, 64, 2}; }
-static size_t grouped_elems(int C, long len) { return (size_t)((C + 31) / 32) * 64 * (size_t)len; }
+inline Lay row_major(long len) { return Lay{(size_t)64 * len, 2, (size_t)2 * len}; }
+inline Lay grouped(long len) { return Lay{(size_t)64 * len, 64, 2}; }
+inline size_t grouped_elems(int C, long len) { return (size_t)((C + 31) / 32) * 64 * (size_t)len; }
+inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
+// out = P P, row-major n x n (n <= 8, out may be P): every product summed in k order without FMA
+inline void mat_square(const double *P, double *out, int n) {
+    double t[64];
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double acc = 0.0;
+            for (int k = 0; k < n; ++k) acc = acc + P[i * n + k] * P[k * n + j];
+            t[i * n + j] = acc;
+        }
+    for (int i = 0; i < n * n; ++i) out[i] = t[i];
+}
+
+// The time-blocked (latency mode) decimator's and filtfilt's tiles, and the shapes they serve.
+constexpr int SB_B = 256;        // decimator: samples per tile
+constexpr int SB_MAXT = 1024;    // tiles per stream (one scan workgroup): L <= 262144
+constexpr int SB_NPOW = 10;      // Phi^(2^r), r < SB_NPOW: covers SB_MAXT tiles
+constexpr int SB_MAXC = 64;      // channels up to which tetra_demod_compat takes this path
+constexpr int SB_MAXQ = 16;      // decimation factors up to which it does
+constexpr int LB_B = 128;        // filtfilt: samples per tile
+constexpr int LB_NS = 4;         // states (butter(4): 5 taps)
+inline bool blocked_fits(int C, long N, int q) {
+    return C >= 1 && C <= SB_MAXC && q >= 2 && q <= SB_MAXQ && N > 27 && (N + 54 + SB_B - 1) / SB_B <= SB_MAXT;
+}
+inline bool lf_blocked_fits(int C, long M, int ntaps) {
+    return C >= 1 && C <= SB_MAXC && ntaps == LB_NS + 1 && (M + 6 * ntaps + LB_B - 1) / LB_B <= SB_MAXT;
+}
+
+// The compat path's sample formats: the element size of cf32 / cf64, or 0 with the error set.
+inline size_t compat_elem_size(tetra_ctx *ctx, int fmt) {
+    if (fmt == TETRA_CF32 || fmt == TETRA_CF64) return fmt == TETRA_CF64 ? 8 : 4;
+    tetra_fail(ctx, TETRA_E_INVALID, "compat path takes cf32/cf64");
+    return 0;
+}
+int check_plan(tetra_ctx *ctx, const tetra_compat_plan *P);   // compat_demod.hip
+
+// Stage entry points: samples as untyped pointers with their format (TETRA_CF32 / CF64), which each
+// unit resolves to float / double once.  compat_decimate.hip (DEC_TILED: cf32 only):
+enum DecForm { DEC_SEQUENTIAL, DEC_BLOCKED, DEC_TILED };
+int compat_decimate(tetra_ctx *ctx, const tetra_compat_plan *P, int fmt, DecForm form, const void *x, int C, long N,
+                    void *out, Lay lo);
+void blocked_table(const double *coef /*[24] sos rows*/, double *tab /*[SB_NPOW * 64]*/);
+// compat_filtfilt.hip: frequency_shift of the rows with mixon set (all when it is null), and filtfilt
+// with that mixer inside the recursion, after k_mix (LF_PREMIX: every row mixed) or time-blocked.
+enum LfForm { LF_SEQUENTIAL, LF_PREMIX, LF_BLOCKED };
+int launch_mix(tetra_ctx *ctx, int fmt, const void *x, Lay lx, int C, long N, const double *mixc,
+                const uint8_t *mixon, double fs, double *out, Lay lo);
+int compat_filtfilt(tetra_ctx *ctx, const tetra_compat_plan *P, int fmt, LfForm form, const void *x, Lay lx, int C,
+                    long M, const double *mixc, const uint8_t *mixon, double *out, Lay lo);
+void lfilter_table(const double *bcoef, const double *acoef, double *tab /*[SB_NPOW * 16]*/);
+// compat_symbols.hip: extract_symbols (over the |y|^2 rows pw when given), then demodulate_dqpsk.
+void compat_extract_decide(tetra_ctx *ctx, const tetra_compat_plan *P, int fmt, const void *y, Lay ly, int C, long M,
+                           void *sym, int32_t *nsym, long smax, void *pw, uint8_t *hard);
+
+// The decimator's coefficients in precision T (24 sos words, 8 of sosfilt_zi) to `coef`, sos to dc
+template <typename T>
+int upload_sos_coef(tetra_ctx *ctx, const tetra_compat_plan *P, T *coef, double *dc = nullptr) {
+    T hc[32];
+    for (int i = 0; i < 24; ++i) hc[i] = std::is_same<T, float>::value ? (T)P->sos_f32[i] : (T)P->sos_f64[i];
+    for (int i = 0; i < 8; ++i) hc[24 + i] = std::is_same<T, float>::value ? (T)P->zi_f32[i] : (T)P->zi_f64[i];
+    for (int i = 0; dc && i < 24; ++i) dc[i] = (double)hc[i];
+    HIP_TRY(ctx, hipMemcpyAsync(coef, hc, sizeof hc, hipMemcpyHostToDevice, ctx->stream));
+    return TETRA_OK;
+}
+
+namespace {
 
 constexpr int NSEC = 4;   // decimate's cheby1(8) -> 4 second-order sections
 

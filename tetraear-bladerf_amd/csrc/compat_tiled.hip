@@ -1,5 +1,5 @@
 // compat_tiled.hip -- decimate's fp32 sosfiltfilt cut into time tiles, bit-identical to the
-// sequential kernels of compat_demod.hip (TETRA_COMPAT_TILED, opt-in).
+// sequential kernels of compat_decimate.hip (TETRA_COMPAT_TILED, opt-in).
 //
 // The cheby1(8) recursion forgets its start: run from an all-zero state TL_WARM samples early, its
 // fp32 state is usually the sequential run's, bit for bit, by the time the tile begins.  That is
@@ -308,8 +308,6 @@ __global__ __launch_bounds__(256) void k_tl_resolve(const float *__restrict__ x,
     }
 }
 
-long tl_ceil_div(long a, long b) { return (a + b - 1) / b; }
-
 template <int QT>
 void tl_launch(tetra_ctx *ctx, const float *x, float *scr, float *out, Lay lo, const TlGeo &G, const float *coef,
                float2 *Sst, float2 *Est, int32_t *stats) {
@@ -345,7 +343,7 @@ int run_decimate_tiled(tetra_ctx *ctx, const tetra_compat_plan *P, const float *
     const long L = N + 2 * TL_PAD;
     const long Lp = (L + 3) & ~3L;
     const int T = ctx->tl_tile > 0 ? ctx->tl_tile : TL_TILE, W = ctx->tl_warm > 0 ? ctx->tl_warm : TL_WARM;
-    const TlGeo G{C, (int)tl_ceil_div(L, T), T, W, N, L, Lp};
+    const TlGeo G{C, (int)ceil_div(L, T), T, W, N, L, Lp};
     const size_t nst = (size_t)2 * C * G.K * 4;   // float2 state words per array
     float *scr = (float *)ws(ctx, S_W0, (size_t)2 * C * Lp * sizeof(float));
     float *coef = (float *)ws(ctx, S_W7, 32 * sizeof(float));
@@ -353,10 +351,8 @@ int run_decimate_tiled(tetra_ctx *ctx, const tetra_compat_plan *P, const float *
     if (!scr || !coef || !tl) return TETRA_E_NOMEM;
     int32_t *stats = (int32_t *)tl;
     float2 *Sst = (float2 *)(tl + 16), *Est = Sst + nst;
-    float hc[32];
-    for (int i = 0; i < 24; ++i) hc[i] = P->sos_f32[i];
-    for (int i = 0; i < 8; ++i) hc[24 + i] = P->zi_f32[i];
-    HIP_TRY(ctx, hipMemcpyAsync(coef, hc, sizeof hc, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = upload_sos_coef(ctx, P, coef);
+    if (rc) return rc;
     HIP_TRY(ctx, hipMemsetAsync(stats, 0, 16, ctx->stream));
     switch (P->q) {
         case 7: tl_launch<7>(ctx, x, scr, out, lo, G, coef, Sst, Est, stats); break;
@@ -401,7 +397,7 @@ int tetra_decimate_tiled(tetra_ctx *ctx, const tetra_compat_plan *P, const void 
         ctx->tl_ran = false;
         return tetra_decimate(ctx, P, iq, fmt, C, N, out);   // the sequential kernels: exact either way
     }
-    const size_t M = (size_t)tl_ceil_div((long)N, P->q);
+    const size_t M = (size_t)ceil_div((long)N, P->q);
     Staging st(ctx);
     const void *x = st.in(iq, C * N * 8);
     void *o = st.out(out, C * M * 8);
