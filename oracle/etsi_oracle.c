@@ -322,7 +322,7 @@ void eo_om_quarters(const float *y, int M2, float A[4])
 }
 
 /* The same class sums in the wideband chain's grouped order (the resampler forms them while it
- * writes y; csrc/wideband.hip k_pfb_resamp_fix OM, etsi_demod.hip k_timing OMG).  The chunk is
+ * writes y; csrc/wideband.hip k_pfb_resamp_fix OM, etsi_timing.hip k_timing OMG).  The chunk is
  * row[s, s + M2) of a carrier's 72 kHz row, s and M2 multiples of 4 and U (the resampler's output
  * group) a multiple of 4, so class c is n mod 4 in row positions too.
  *   group partials P[g][c] = sum over o = c mod 4 in [0, U), ascending, of |row[U g + o]|^2;

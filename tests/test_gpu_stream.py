@@ -98,6 +98,7 @@ _LAUNCHES = {"skip": set(), "fused": {"etsi_demod"}, "pair": {"etsi_chanfilt", "
     ([40, 50002, 50000, 3000], ["skip", "fused", "fused", "fused"]),
     ([134410, 134408], ["pair", "pair"]),
     ([131072, 131072], ["fused", "fused"]),
+    ([131072, 131072], {"pad": 2, "cf32": ["fused", "fused"], "sc16": ["fused", "pair"]}),
 ])
 def test_stream_every_demod_path_vs_oracle(sizes, paths, fmt):
     """Every launch path of tetra_demod_etsi_stream, chunk by chunk against the oracle stream (nsym,
@@ -109,9 +110,20 @@ def test_stream_every_demod_path_vs_oracle(sizes, paths, fmt):
     [134410, 134408]: M2 = 4000 > YLDS in the first window and more in the second -- the unfused
     k_chanfilt + k_timing pair with track, yoff > 0 and an acquired loop (SC16 rows not a multiple
     of four samples);
-    [131072, 131072]: the per-wave fused kernel for both formats."""
+    [131072, 131072]: the per-wave fused kernel for both formats;
+    the same with pad = 2: the windows (W = 0 mod 4: 131072, then 132444) lie in rows of pitch
+    W + 2 = 2 (mod 4), so SC16's rows are not whole 16-B groups and it takes k_chanfilt -- fused for
+    the first window, and for the second (M2 = 3940, 988 symbol rows: 4928 > the 4920 float2 of
+    k_chanfilt<uint2>'s LDS, where the per-wave kernel would still fuse) the pair; cf32 stays
+    per-wave.  The stage names do not tell the two fused kernels apart (both record etsi_demod), and
+    tetra_etsi_kernel_info names a kernel for ld = N only: in this row it is the second window's pair
+    that shows the pitch kept SC16 off the per-wave kernel; the first pins k_chanfilt<uint2>'s fused
+    results on such rows."""
     from tetraear import _hip
     from tetraear.signal.etsi import EtsiStream, synth
+    pad = 0
+    if isinstance(paths, dict):   # a row with a row pitch of its own and the paths per format
+        pad, paths = paths["pad"], paths[fmt]
     C, total = 2, sum(sizes)
     iq = synth(C, total, seed=67, snr_db=18.0, cfo_max=600.0)[0]
     inp = iq
@@ -126,7 +138,7 @@ def test_stream_every_demod_path_vs_oracle(sizes, paths, fmt):
     try:
         _profile_stages(c)   # drop earlier records
         for k, (at, n) in enumerate(plan):
-            d = st.demod(inp[:, at:at + n])
+            d = st.demod(inp[:, at:at + n], row_pad=pad)
             assert _profile_stages(c) & _DEMOD_STAGES == _LAUNCHES[paths[k]], (k, paths[k])
             if paths[k] == "skip":
                 assert not d[3].any()

@@ -114,8 +114,9 @@ def test_summaries_carry_source_provenance_and_bench_rejects_stale(tmp_path):
     sys.path.insert(0, REPO)
     import bench
     src = P.kernel_source("k_chanfilt_r")
-    assert src and src["file"] == "etsi_demod.hip" and len(src["sha256"]) == 64
-    assert P.kernel_source("k_timing")["file"] == "etsi_demod.hip"
+    assert src and src["file"] == "etsi_chanfilt_r.hip" and len(src["sha256"]) == 64
+    assert P.kernel_source("k_chanfilt")["file"] == "etsi_chanfilt.hip"
+    assert P.kernel_source("k_timing")["file"] == "etsi_timing.hip"
     assert P.kernel_source("k_etsi_viterbi")["file"] == "etsi_lmac.hip"
     assert P.kernel_source("k_sos_fwd_bank")["file"] == "compat_decimate.hip"
     assert P.kernel_source("k_lf_fwd")["file"] == "compat_filtfilt.hip"
@@ -136,3 +137,50 @@ def test_summaries_carry_source_provenance_and_bench_rejects_stale(tmp_path):
     assert t["bytes"] is None and "other code" in t["reason"]
     t = bench.traffic_from_profiles("k_chanfilt_r", "no such workload", profiles=str(prof))
     assert t["bytes"] is None and "no rocprofv3" in t["reason"]
+
+
+def _csrc(tmp_path, files):
+    d = tmp_path / "csrc"
+    d.mkdir()
+    for name, text in files.items():
+        (d / name).write_bytes(text)
+    return str(d)
+
+
+_TREE = {
+    "common.h": b'#pragma once\n#include "../../include/tetra_hip.h"\nstruct Ctx {};\n',
+    "inner.h": b"#pragma once\nconstexpr int INNER = 1;\n",
+    "outer.h": b'#pragma once\n#include "common.h"\n#include "inner.h"\nconstexpr int OUTER = INNER;\n',
+    "other.h": b"#pragma once\nconstexpr int OTHER = 2;\n",
+    "a.hip": b'#include "outer.h"\n__global__ void k_a(int *p) { *p = OUTER; }\n',
+    "b.hip": b'#include "common.h"\n__global__ void k_b(int *p) { *p = 0; }\n',
+    "c.hip": b'#include "common.h"\n#include "other.h"\n__global__ void k_c(int *p) { *p = OTHER; }\n',
+}
+
+
+def test_provenance_follows_headers_through_headers(tmp_path):
+    """A kernel's digest covers every csrc header its unit reaches, also through another header, and
+    no header it does not reach."""
+    d = _csrc(tmp_path, _TREE)
+    before = {k: P.kernel_source(k, csrc=d) for k in ("k_a", "k_b", "k_c")}
+    assert [before[k]["file"] for k in ("k_a", "k_b", "k_c")] == ["a.hip", "b.hip", "c.hip"]
+    with open(os.path.join(d, "inner.h"), "ab") as f:   # reached by a.hip only, through outer.h
+        f.write(b"// edited\n")
+    after = {k: P.kernel_source(k, csrc=d) for k in ("k_a", "k_b", "k_c")}
+    assert after["k_a"]["sha256"] != before["k_a"]["sha256"]
+    assert after["k_b"] == before["k_b"] and after["k_c"] == before["k_c"]
+    with open(os.path.join(d, "other.h"), "ab") as f:   # unrelated to a.hip and b.hip
+        f.write(b"// edited\n")
+    last = {k: P.kernel_source(k, csrc=d) for k in ("k_a", "k_b", "k_c")}
+    assert last["k_a"] == after["k_a"] and last["k_b"] == after["k_b"]
+    assert last["k_c"]["sha256"] != after["k_c"]["sha256"]
+
+
+def test_provenance_of_a_unit_with_only_common_h_is_unchanged(tmp_path):
+    """sha256(file + common.h), as before headers were followed: the summaries of such units stay
+    valid; with more headers the order is file, common.h, then the others by name, each once."""
+    import hashlib
+    d = _csrc(tmp_path, _TREE)
+    assert P.kernel_source("k_b", csrc=d)["sha256"] == hashlib.sha256(_TREE["b.hip"] + _TREE["common.h"]).hexdigest()
+    assert P.kernel_source("k_a", csrc=d)["sha256"] == hashlib.sha256(
+        _TREE["a.hip"] + _TREE["common.h"] + _TREE["inner.h"] + _TREE["outer.h"]).hexdigest()

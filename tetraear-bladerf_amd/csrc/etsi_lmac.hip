@@ -1,5 +1,5 @@
 // etsi_lmac.hip -- ETSI EN 300 392-2 lower MAC on gfx950: burst sync and channel decoding of the
-// rows etsi_demod.hip's timing stage writes (hard dibits, int8 soft bits, nsym), the second half
+// rows the ETSI timing stage (etsi_timing.h) writes (hard dibits, int8 soft bits, nsym), the second half
 // of the north-star receive chain, restating oracle/etsi_oracle.c bit for bit.
 //
 //   k_etsi_sync  one wave per channel: hard bits packed by ballots, head/training/tail correlation

@@ -3,7 +3,7 @@
 // The reference's CLI takes the sample rate as an argument and its GUI slider spans 1.8-2.4 MSps
 // in 0.1 MHz steps (/root/reference/tetraear/ui/modern.py:5518-5519, 5630-5638); process() takes
 // whatever rate the SignalProcessor was built for (processor.py:245-257).  The fused kernels of
-// etsi_demod.hip are specialised for 2.4 MSps (stage 1 / 10, stage 2 x3/10 on MFMA).  Every other
+// etsi_chanfilt_r.hip and etsi_chanfilt.hip are specialised for 2.4 MSps (stage 1 / 10, stage 2 x3/10 on MFMA).  Every other
 // rate runs here: stage 1 = L1-tap FIR decimating by q1, stage 2 = polyphase RRC x up/down to
 // 72 kHz, written to HBM for k_timing.  The arithmetic restates oracle/etsi_oracle.c eo_chanfilt
 // operation for operation -- stage 1 one fmaf chain per component over j ascending, stage 2 one

@@ -1,6 +1,6 @@
 // wideband.hip -- C3: a 20 MSps wideband capture split into M = 800 carriers at
 // 25 kHz spacing by a polyphase filter bank (PFB), each carrier resampled to 72 kHz (4 samples
-// per symbol) for the ETSI timing stage (etsi_rx.hip k_timing) and lower MAC.
+// per symbol) for the ETSI timing stage (etsi_timing.hip k_timing) and lower MAC.
 //
 // The reference tunes the SDR to one carrier per capture (capture.py, modern.py:1886-2034); this
 // is the channeliser BASELINE.json's north_star names, so oracle/wideband.py (float64 numpy) is

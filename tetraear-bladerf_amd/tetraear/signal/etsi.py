@@ -152,9 +152,12 @@ class EtsiStream:
         self.hist = None
         self.diag = None
 
-    def demod(self, iq, freq_offsets=None):
+    def demod(self, iq, freq_offsets=None, row_pad=0):
         """[C, n] complex or [C, n, 2] int16 SC16 (n even) -> (hard [C, smax] u8, soft_bits
-        [C, 2*smax] i8, symbols [C, smax] c64, nsym [C]) of this chunk, rows as described above."""
+        [C, 2*smax] i8, symbols [C, smax] c64, nsym [C]) of this chunk, rows as described above.
+        row_pad (for tests; applications leave it 0): the windows are handed to the library in rows of
+        W + row_pad samples (even for SC16), as windows of a capture resident in wider rows are -- the
+        kernel choice depends on the row pitch, and this is how a test reaches it from host windows."""
         iq = np.asarray(iq)
         if iq.dtype == np.int16:
             if iq.ndim != 3 or iq.shape[-1] != 2:
@@ -192,6 +195,10 @@ class EtsiStream:
             dwin = mixed
         else:
             dwin = win
+        if row_pad:
+            wide = np.zeros((self.C, W + int(row_pad)) + dwin.shape[2:], dwin.dtype)
+            wide[:, :W] = dwin
+            dwin = wide
         _, M2, sm = lengths(self.plan, W)
         smax = max(sm + 1, 2)
         sym = np.zeros((self.C, smax), np.complex64)
@@ -199,7 +206,7 @@ class EtsiStream:
         hard = np.zeros((self.C, smax), np.uint8)
         ns = np.zeros(self.C, np.int32)
         diag = np.zeros((self.C, 4), np.float32)
-        c.check(c.lib.tetra_demod_etsi_stream(c.handle, self.plan, _hip.ptr(dwin), fmt, self.C, W, W, int(yoff),
+        c.check(c.lib.tetra_demod_etsi_stream(c.handle, self.plan, _hip.ptr(dwin), fmt, self.C, dwin.shape[1], W, int(yoff),
                                               _hip.ptr(self.track), _hip.ptr(sym), _hip.ptr(soft), _hip.ptr(hard),
                                               _hip.ptr(ns), smax, smax, _hip.ptr(diag)), "tetra_demod_etsi_stream")
         keep = min(self.HIST, win.shape[1])

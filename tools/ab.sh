@@ -3,7 +3,7 @@
 # DESIGN.md (records: profiles/r0*_ab_*.txt).  Boxes differ by up to +-5 %, so variants are only ever
 # compared inside one gpurun call, three rounds interleaved.
 #
-#   tools/ab.sh build NAME SPEC [SRC]   lib/variants/libNAME.so, csrc/SRC.hip (default etsi_demod) changed by
+#   tools/ab.sh build NAME SPEC [SRC]   lib/variants/libNAME.so, csrc/SRC.hip (default etsi_chanfilt_r) changed by
 #        SPEC = tools/ab_patches/X.py   a python filter (stdin -> stdout; timing-only patches: a phase
 #                                       skipped, outputs wrong -- never #ifdefs in the product kernels)
 #             | tools/ab_patches/X.sed  a sed script
@@ -24,7 +24,7 @@ summ() {   # one line per run: label, ms/step, per-stage ms, read floor
 }
 case $cmd in
 build)
-    NAME=$1; SPEC=$2; SRC=${3:-etsi_demod}
+    NAME=$1; SPEC=$2; SRC=${3:-etsi_chanfilt_r}
     cd $R/tetraear-bladerf_amd
     make -s
     mkdir -p build/var lib/variants

@@ -35,9 +35,28 @@ MARK = "k_region_mark"
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tetraear-bladerf_amd", "csrc")
 
 
+_INCLUDE = re.compile(rb'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
+
+
+def _headers(text, csrc):
+    """Names of the headers under csrc that `text` reaches through quoted #includes, transitively
+    (an include that leaves csrc, such as common.h's of the public header, is not followed)."""
+    seen, todo = set(), [text]
+    while todo:
+        for name in _INCLUDE.findall(todo.pop()):
+            name = name.decode("utf-8", "replace")
+            path = os.path.join(csrc, name)
+            if name in seen or os.path.basename(name) != name or not os.path.isfile(path):
+                continue
+            seen.add(name)
+            todo.append(open(path, "rb").read())
+    return seen
+
+
 def kernel_source(short_name, csrc=CSRC):
-    """Provenance of a kernel's code: {"file": <csrc file defining it>, "sha256": <hash of that file
-    and common.h>} or None.  pmc_summary records it per kernel; bench.py accepts a summary's bytes
+    """Provenance of a kernel's code: {"file": <csrc file defining it>, "sha256": <hash of that file,
+    common.h, then every other csrc header the file includes, directly or through another header, in
+    sorted name order>} or None.  pmc_summary records it per kernel; bench.py accepts a summary's bytes
     only while the kernel's source still hashes the same, so a summary of older code is never cited
     (VERDICT r5 item 4).  No git needed: the GPU box gets the tree without .git."""
     pat = re.compile(r"\bvoid\s+" + re.escape(short_name) + r"\s*\(")
@@ -48,6 +67,8 @@ def kernel_source(short_name, csrc=CSRC):
             h = hashlib.sha256(text)
             if os.path.isfile(common):
                 h.update(open(common, "rb").read())
+            for name in sorted(_headers(text, csrc) - {"common.h"}):
+                h.update(open(os.path.join(csrc, name), "rb").read())
             return {"file": os.path.basename(f), "sha256": h.hexdigest()}
     return None
 FETCH_CORRECTION = 2   # calibrated at 4, 8 and 16 B per lane (docstring)
