@@ -423,6 +423,25 @@ int tetra_lmac_etsi(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard,
 int tetra_lmac_etsi_acquire(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym,
                             size_t C, size_t smax, uint32_t *cell_init, int32_t *nburst, int32_t *bursts,
                             int32_t *nblock, int32_t *blocks, uint8_t *type1);
+/* Cell acquisition per group of rows (a new symbol of ABI version 2; nothing existing changed shape).
+ * Rows g G .. g G + G - 1 are G consecutive pieces of one carrier, in time order -- the wideband
+ * chain's (carrier, chunk) rows, G = chunks per carrier -- and share one cell: cell_init [C / G]
+ * (in/out) and ngood [C / G] (out), host or device.  tetra_lmac_etsi_acquire's rule taken from a row
+ * to a group: the burst scan on every row, every row's BSCH blocks decoded with colour code 0, then
+ * per group the rows in ascending order and each row's bursts in order -- the last CRC-good BSCH
+ * sets cell_init[g] (the same type-1 fields), none keeps it (3 = unknown) -- and every SCH/F and
+ * SCH/HD block of every row of the group, the rows before the synchronisation burst's included, is
+ * descrambled with cell_init[g].  ngood[g] counts the CRC-good BSCH blocks of the group in this
+ * call: an all-zero cell (MCC = MNC = colour code = 0) has the init of "unknown", so the count, not
+ * the init, says that a cell was heard.  Outputs as tetra_lmac_etsi's, per row.  G >= 1 and
+ * C % G == 0, else TETRA_E_INVALID with nothing written; G = 1 is tetra_lmac_etsi_acquire bit for
+ * bit.  Replaces, for the wideband chain, handing tetra_etsi_set_cells one known init per carrier:
+ * the state the reference parser keeps from a broadcast
+ * (/root/reference/tetraear/core/protocol.py:479-485), kept per carrier over all of its rows. */
+int tetra_lmac_etsi_acquire_groups(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym,
+                                   size_t C, size_t smax, size_t G, uint32_t *cell_init /*[C/G] in/out*/,
+                                   int32_t *ngood /*[C/G] out*/, int32_t *nburst, int32_t *bursts, int32_t *nblock,
+                                   int32_t *blocks, uint8_t *type1);
 /* ---------------------------------------------------------------- streaming (one continuous capture)
  * The reference's callers stream a continuous capture in chunks (modern.py:1901-1919,
  * continuous_capture.py:20); these entry points decode consecutive chunks of each channel as ONE

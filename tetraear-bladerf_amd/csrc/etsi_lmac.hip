@@ -12,6 +12,8 @@
 //   k_etsi_traceback  one lane per job: traceback with the CRC-16 folded in.
 //   k_etsi_tail  streaming: a channel's undecoded tail moved to the front of the next chunk's rows.
 //   k_cell_acquire  one lane per channel: the scrambling init from the chunk's last CRC-good BSCH.
+//   k_cell_acquire_groups  one wave per group of rows (a carrier's chunks): the same rule over the
+//                group's rows in order, the scrambler sequence formed once and stored to its rows.
 //   k_decode_blocks, k_encode_blocks  the channel coding of independent blocks of one kind
 //                (component entry points: tetra_etsi_decode_blocks / _encode_blocks).
 #include <cstdlib>
@@ -632,6 +634,111 @@ __global__ __launch_bounds__(256) void k_cell_acquire(int C, const int32_t *__re
     }
 }
 
+// --------------------------------------------------------------------------- grouped cell acquisition
+// The scrambler is linear over GF(2): with x[0..31] the init's bits and x[n + 32] = XOR over the
+// taps t of x[n + t], its output bit n is x[n + 32] = parity(init & SCR_MASK.w[n]).  The table lets
+// a wave form all 432 bits at once (a lane four of them) where k_cell_acquire steps the register.
+struct ScrMask {
+    alignas(16) uint32_t w[432];
+};
+constexpr ScrMask make_scr_mask() {
+    ScrMask m{};
+    uint32_t x[32 + 432] = {};
+    for (int i = 0; i < 32; ++i) x[i] = 1u << i;
+    for (int n = 0; n < 432; ++n) {
+        uint32_t v = 0;
+        for (int t = 0; t < 32; ++t)
+            if ((SCR_TAPS >> t) & 1u) v ^= x[n + t];
+        x[n + 32] = v;
+        m.w[n] = v;
+    }
+    return m;
+}
+__constant__ ScrMask SCR_MASK = make_scr_mask();
+
+// One WAVE per group of G rows (tetra_lmac_etsi_acquire_groups), after the BSCH blocks of every row
+// are decoded: k_cell_acquire's rule over the group's rows in ascending order and each row's bursts
+// in order.  Lane i of a step looks at (row i >> 3, burst i & 7); a ballot counts the CRC-good BSCH
+// blocks and names the last one, whose type-1 fields a second ballot packs into the init (lane j
+// reads the bit that lands at bit j).  The group's scrambler sequence is formed once (SCR_MASK, a
+// lane's dwords w = lane and lane + 64) and stored as whole dwords to the 432-byte table row of every
+// row of the group whose tab_init differs: the table stays per row, as k_etsi_viterbi reads it.
+constexpr int ACQ_WAVES = 4;   // groups per workgroup (the waves share nothing)
+
+__global__ __launch_bounds__(64 * ACQ_WAVES) void k_cell_acquire_groups(
+    int NG, int G, const int32_t *__restrict__ nburst, const int32_t *__restrict__ bursts,
+    const int32_t *__restrict__ blocks, const uint8_t *__restrict__ type1, uint32_t *__restrict__ cell_init /*[NG]*/,
+    int32_t *__restrict__ ngood /*[NG]*/, uint32_t *__restrict__ tab_init /*[NG G]*/, uint8_t *__restrict__ cell_scr) {
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * ACQ_WAVES + (threadIdx.x >> 6);
+    if (g >= NG) return;   // the whole wave
+    const size_t row0 = (size_t)g * G;
+    // block slot of burst b of a row: the sync kernel's numbering (1 per NDB(n), 2 per NDB(p) / SB)
+    auto slot_of = [&](size_t ch, int b) {
+        int q = 0;
+        for (int p = 0; p < b; ++p) q += bursts[(ch * ETSI_MAXB + p) * 2 + 1] == 0 ? 1 : 2;
+        return q;
+    };
+    int good = 0, last = -1;   // wave-uniform: CRC-good BSCH blocks, the last one's (row, burst) index
+    for (int i0 = 0; i0 < ETSI_MAXB * G; i0 += 64) {
+        const int i = i0 + lane, r = i / ETSI_MAXB, b = i % ETSI_MAXB;
+        bool ok = false;
+        if (r < G) {
+            const size_t ch = row0 + r;
+            if (b < min(nburst[ch], ETSI_MAXB) && bursts[(ch * ETSI_MAXB + b) * 2 + 1] == 2) {
+                const int q = slot_of(ch, b);
+                ok = q < ETSI_MAXJ && blocks[(ch * ETSI_MAXJ + q) * 4 + 1] != 0;
+            }
+        }
+        const unsigned long long bal = __ballot(ok);
+        if (bal) {
+            good += __popcll(bal);
+            last = i0 + 63 - __clzll((long long)bal);
+        }
+    }
+    uint32_t init = cell_init[g];
+    if (last >= 0) {
+        const size_t ch = row0 + last / ETSI_MAXB;
+        const uint8_t *t = type1 + (ch * ETSI_MAXJ + slot_of(ch, last % ETSI_MAXB)) * 268;
+        // lanes 0..5: colour code bit j = type-1 bit 9 - j; lanes 8..31: bit j - 8 of MCC(10) MNC(14),
+        // type-1 bit 62 - j (the fields are MSB first)
+        const bool use = lane < 6 || (lane >= 8 && lane < 32);
+        const uint32_t bit = use ? t[lane < 6 ? 9 - lane : 62 - lane] & 1u : 0u;
+        const unsigned long long f = __ballot(bit != 0);
+        const uint32_t ecc = (uint32_t)f & 0x3Fu, mm = (uint32_t)(f >> 8) & 0xFFFFFFu;
+        init = (((mm << 6) | ecc) << 2) | 3u;
+    }
+    if (lane == 0) {
+        cell_init[g] = init;
+        ngood[g] = good;
+    }
+    uint32_t v0 = 0, v1 = 0;   // the sequence's dwords lane and 64 + lane (four 0 / 1 bytes each)
+    bool have = false;
+    for (int r0 = 0; r0 < G; r0 += 64) {
+        const int r = r0 + lane;
+        const bool need = r < G && tab_init[row0 + r] != init;
+        unsigned long long m = __ballot(need);
+        if (m && !have) {
+            auto dword = [&](int w) {
+                const uint4 k = *reinterpret_cast<const uint4 *>(&SCR_MASK.w[4 * w]);
+                return ((uint32_t)__popc(init & k.x) & 1u) | (((uint32_t)__popc(init & k.y) & 1u) << 8) |
+                       (((uint32_t)__popc(init & k.z) & 1u) << 16) | (((uint32_t)__popc(init & k.w) & 1u) << 24);
+            };
+            v0 = dword(lane);
+            v1 = dword(min(lane + 64, 107));
+            have = true;
+        }
+        if (need) tab_init[row0 + r] = init;
+        while (m) {   // wave-uniform: one coalesced 432-byte store per row
+            const int rr = r0 + __ffsll((long long)m) - 1;
+            m &= m - 1;
+            uint32_t *o = reinterpret_cast<uint32_t *>(cell_scr + (row0 + rr) * 432);
+            o[lane] = v0;
+            if (lane < 44) o[64 + lane] = v1;
+        }
+    }
+}
+
 // --------------------------------------------------------------------------- component kernels
 // Block decode of F independent blocks of one kind (16 lanes per block, 4 per wave).
 __global__ __launch_bounds__(64) void k_decode_blocks(const int8_t *__restrict__ soft5, int F, int kind,
@@ -811,11 +918,13 @@ int tetra_etsi_encode_blocks(tetra_ctx *ctx, const uint8_t *type1, size_t F, int
 }
 
 // The lower MAC's launch sequence; cell_init (device) selects acquisition, else the configured cells.
+// G > 0 (with ngood): acquisition per group of G rows, cell_init and ngood C / G long.
 static int lmac_etsi(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym, size_t C,
                      size_t smax, uint32_t *cell_init, int32_t *nburst, int32_t *bursts, int32_t *nblock,
                      int32_t *blocks, uint8_t *type1, int32_t *lead = nullptr, int8_t *next_soft = nullptr,
-                     uint8_t *next_hard = nullptr) {
+                     uint8_t *next_hard = nullptr, size_t G = 0, int32_t *ngood = nullptr) {
     if (!ctx || C == 0) return TETRA_E_INVALID;
+    const size_t ncell = G ? C / G : C;   // acquisition states
     if (!cell_init && ctx->cells < C)
         return tetra_fail(ctx, TETRA_E_INVALID, "tetra_etsi_set_cells() for %zu channels first", C);
     if (2 * smax > LMAC_MAXBITS + 4) return tetra_fail(ctx, TETRA_E_INVALID, "chunk too long for tetra_lmac_etsi");
@@ -823,7 +932,8 @@ static int lmac_etsi(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard
     if (C * smax * 2 + 8 > (size_t)INT32_MAX || (C + 1) * 432 > (size_t)INT32_MAX)
         return tetra_fail(ctx, TETRA_E_INVALID, "too many channels for one tetra_lmac_etsi call (%zu)", C);
     Staging st(ctx);
-    uint32_t *ci = cell_init ? (uint32_t *)st.inout(cell_init, C * 4) : nullptr;
+    uint32_t *ci = cell_init ? (uint32_t *)st.inout(cell_init, ncell * 4) : nullptr;
+    int32_t *ngo = G ? (int32_t *)st.out(ngood, ncell * 4) : nullptr;
     // streaming into the input rows themselves: host rows are staged in and back out (with the tail)
     const bool alias = lead && next_soft == softbits;
     const int8_t *sb = alias ? (const int8_t *)st.inout(const_cast<int8_t *>(softbits), C * smax * 2)
@@ -849,7 +959,7 @@ static int lmac_etsi(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard
     // workspace: [job counters per kind (16 B)] [jobs] [survivors: 36 groups x jtot x 4 lanes x 32 bits
     // (SCH/F: 288 steps / 8; allocated as 288 x jtot dwords)]
     char *w = (char *)ws(ctx, S_W7, 16 + jtot * sizeof(Job) + 288 * jtot * 4 + (lead ? 8 * C : 0));
-    if ((cell_init && !ci) || !sb || !hd || !ns || !nbo || !bo || !nko || !ko || !to || !w) return st.finish();
+    if ((cell_init && !ci) || (G && !ngo) || !sb || !hd || !ns || !nbo || !bo || !nko || !ko || !to || !w) return st.finish();
     unsigned long long *jcount = (unsigned long long *)w;
     Job *jobs = (Job *)(w + 16);
     uint32_t *surv = (uint32_t *)(w + 16 + jtot * sizeof(Job));
@@ -892,8 +1002,13 @@ static int lmac_etsi(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard
         hipLaunchKernelGGL(k_etsi_viterbi, vgrid(4), dim3(64), 0, ctx->stream, jobs, jcount, (int)C, sb, (int)smax,
                            cells, bsch_scr, surv, 4);
         hipLaunchKernelGGL(k_etsi_traceback, tgrid(4), dim3(64), 0, ctx->stream, jobs, jcount, (int)C, surv, ko, to, 4);
-        hipLaunchKernelGGL(k_cell_acquire, dim3(grid_for(C, 256)), dim3(256), 0, ctx->stream, (int)C, nbo, bo, ko, to,
-                           ci, (uint32_t *)ctx->slot[S_W14].p, cells);
+        if (G)
+            hipLaunchKernelGGL(k_cell_acquire_groups, dim3(grid_for(ncell, ACQ_WAVES)), dim3(64 * ACQ_WAVES), 0,
+                               ctx->stream, (int)ncell, (int)G, nbo, bo, ko, to, ci, ngo,
+                               (uint32_t *)ctx->slot[S_W14].p, cells);
+        else
+            hipLaunchKernelGGL(k_cell_acquire, dim3(grid_for(C, 256)), dim3(256), 0, ctx->stream, (int)C, nbo, bo, ko,
+                               to, ci, (uint32_t *)ctx->slot[S_W14].p, cells);
         mask = 3;
     }
     {
@@ -924,6 +1039,17 @@ int tetra_lmac_etsi_acquire(tetra_ctx *ctx, const int8_t *softbits, const uint8_
                             int32_t *nblock, int32_t *blocks, uint8_t *type1) {
     if (!cell_init) return tetra_fail(ctx, TETRA_E_INVALID, "cell_init is NULL");
     return lmac_etsi(ctx, softbits, hard, nsym, C, smax, cell_init, nburst, bursts, nblock, blocks, type1);
+}
+
+int tetra_lmac_etsi_acquire_groups(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym,
+                                   size_t C, size_t smax, size_t G, uint32_t *cell_init, int32_t *ngood,
+                                   int32_t *nburst, int32_t *bursts, int32_t *nblock, int32_t *blocks,
+                                   uint8_t *type1) {
+    if (!cell_init || !ngood) return tetra_fail(ctx, TETRA_E_INVALID, "cell_init or ngood is NULL");
+    if (G == 0 || C % G != 0)
+        return tetra_fail(ctx, TETRA_E_INVALID, "lmac_etsi_acquire_groups: %zu rows are not whole groups of %zu", C, G);
+    return lmac_etsi(ctx, softbits, hard, nsym, C, smax, cell_init, nburst, bursts, nblock, blocks, type1, nullptr,
+                     nullptr, nullptr, G, ngood);
 }
 
 int tetra_lmac_etsi_stream(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym,

@@ -140,6 +140,8 @@ def _bind(L):
         "tetra_etsi_kernel_info": (_i32, [_vp, ctypes.POINTER(EtsiPlan), _i32, _sz, _i32, ctypes.c_char_p, _sz, _vp]),
         "tetra_lmac_etsi": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
         "tetra_lmac_etsi_acquire": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "tetra_lmac_etsi_acquire_groups": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp]),
         "tetra_etsi_stream_window": (_i32, [ctypes.POINTER(EtsiPlan), ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                             _vp, _vp, _vp, _vp]),
         "tetra_demod_etsi_stream": (_i32, [_vp, ctypes.POINTER(EtsiPlan), _vp, _i32, _sz, _sz, _sz, ctypes.c_int,

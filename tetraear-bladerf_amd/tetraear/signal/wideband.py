@@ -208,11 +208,30 @@ class WidebandReceiver:
                 ns.reshape(M, ck.nchunk))
 
 
-    def decode(self, x, cells):
+    def decode(self, x, cells, mac=False):
         """x [Nw] -> per carrier the frames decoded from it, each burst once (merge_chunks), in row
         order: demod, then the ETSI lower MAC on every (carrier, chunk) with carrier k's scrambling
         init cells[k].  A frame is the lower MAC's dict (core/etsi.py) plus "chunk" and "sample" (its
-        start in the carrier's 72 kHz row, to within the timing phase)."""
+        start in the carrier's 72 kHz row, to within the timing phase).  mac=True: every block gains
+        ``npdu`` / ``pdus`` (tetra_etsi_mac's PDU walk, per block; the frames get no tn / fn / mn --
+        a timebase over overlapping chunk rows needs the rows' bursts merged first)."""
+        return self._decode(x, np.asarray(cells, np.uint32), None, mac)[0]
+
+    def decode_acquire(self, x, cell_init, mac=False):
+        """decode without given cells: cell_init [M] holds each carrier's scrambling init before the
+        capture (3 = unknown); every carrier's cell comes from the last CRC-good BSCH over all of its
+        chunk rows, and all of its rows are descrambled with it (tetra_lmac_etsi_acquire_groups, G =
+        chunks per carrier).  Returns (frames as decode's, the inits after the capture [M] uint32,
+        ngood [M] int32: the CRC-good BSCH blocks seen per carrier, copies in two chunks counted twice)."""
+        state = np.array(cell_init, np.uint32)
+        if state.shape != (self.plan.M,):
+            raise ValueError(f"cell_init holds {state.shape} inits, the receiver has {self.plan.M} carriers")
+        frames, ngood = self._decode(x, None, state, mac)
+        return frames, state, ngood
+
+    def _decode(self, x, cells, state, mac):
+        """The chain behind decode (cells [M]) and decode_acquire (state [M], updated in place):
+        (frames, ngood or None)."""
         from tetraear.core.etsi import EtsiLowerMac
         hard, soft, _, ns = self.demod(x)
         M, nchunk, sm = hard.shape
@@ -223,13 +242,28 @@ class WidebandReceiver:
         blocks = np.zeros((C, _hip.ETSI_MAXJ, 4), np.int32)
         t1 = np.zeros((C, _hip.ETSI_MAXJ, 268), np.uint8)
         c = _hip.ctx()
-        cc = np.ascontiguousarray(np.repeat(np.asarray(cells, np.uint32), nchunk))
-        c.check(c.lib.tetra_etsi_set_cells(c.handle, _hip.ptr(cc), C), "tetra_etsi_set_cells")
-        c.check(c.lib.tetra_lmac_etsi(c.handle, _hip.ptr(soft.reshape(C, -1)), _hip.ptr(hard.reshape(C, -1)),
-                                      _hip.ptr(ns.reshape(-1)), C, sm, _hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk),
-                                      _hip.ptr(blocks), _hip.ptr(t1)), "tetra_lmac_etsi")
+        rows = (_hip.ptr(soft.reshape(C, -1)), _hip.ptr(hard.reshape(C, -1)), _hip.ptr(ns.reshape(-1)), C, sm)
+        outs = (_hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1))
+        ngood = None
+        if state is None:
+            cc = np.ascontiguousarray(np.repeat(cells, nchunk))
+            c.check(c.lib.tetra_etsi_set_cells(c.handle, _hip.ptr(cc), C), "tetra_etsi_set_cells")
+            c.check(c.lib.tetra_lmac_etsi(c.handle, *rows, *outs), "tetra_lmac_etsi")
+        else:
+            ngood = np.zeros(M, np.int32)
+            c.check(c.lib.tetra_lmac_etsi_acquire_groups(c.handle, *rows, nchunk, _hip.ptr(state), _hip.ptr(ngood),
+                                                         *outs), "tetra_lmac_etsi_acquire_groups")
         keep, _ = merge_chunks(nb, bursts, nk, blocks, M, nchunk, self.m2)
-        frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1)
+        pdus = None
+        if mac:   # the PDU walk is per block; a fresh timebase per row, its slots not reported
+            pdus = EtsiLowerMac(mac=True)._run_mac(c, C, np.ascontiguousarray(ns.reshape(-1)), nb, bursts, nk, blocks,
+                                                  t1, None)
+        frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1, pdus)
+        if mac:
+            for fr in frames:
+                for f in fr:
+                    for key in ("tn", "fn", "mn", "slot_flags"):
+                        del f[key]
         out = [[] for _ in range(M)]
         for ch in range(C):
             for b, f in enumerate(frames[ch]):
@@ -239,7 +273,7 @@ class WidebandReceiver:
                     out[ch // nchunk].append(f)
         for fr in out:
             fr.sort(key=lambda f: f["sample"])
-        return out
+        return out, ngood
 
 
 class WidebandStream:
@@ -252,21 +286,51 @@ class WidebandStream:
     stream positions, bit for bit, and it holds the last CARRY_Y outputs' input: every burst that the
     buffer's end cut is whole in the next one.  The period also holds the filter bank's mixer term
     ((-1)^(k j) at D = M / 2, (-i)^(k j) at M / 4: whole cycles of it), else odd carriers would
-    come out negated."""
+    come out negated.
+
+    ``cells`` [M] scrambling inits: every carrier is descrambled with its own.  ``cells=None``: the
+    stream acquires them (WidebandReceiver.decode_acquire): a carrier's cell is the last CRC-good
+    BSCH of the buffers so far, kept from piece to piece in ``cell_state`` / ``acquired`` (reset()
+    clears them) and read as ``cells``: per carrier (MCC, MNC, colour code), None before the first
+    BSCH -- EtsiLowerMac.cells per carrier.  A burst is reported once, as first decoded: one that a
+    buffer decoded before its carrier's cell was known is not reported again from the next buffer.
+    ``mac=True``: the blocks carry ``npdu`` / ``pdus`` (WidebandReceiver.decode)."""
     CARRY_Y = 2 * BURST_SAMPLES
 
-    def __init__(self, cells, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64):
+    def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False):
         self.rx = WidebandReceiver(fs, M, m2, oversample)
-        self.cells = np.ascontiguousarray(cells, np.uint32)
+        self.acquire, self.mac = cells is None, bool(mac)
+        self._cells = None if self.acquire else np.ascontiguousarray(cells, np.uint32)
         p = self.rx.plan
         blocks = int(np.lcm(p.c.down, p.oversample))   # filter-bank blocks per period
         self.per, self.ups, self.M, self.tol = p.D * blocks, p.c.up * blocks // p.c.down, p.M, tol
         self.reset()
 
+    @property
+    def cells(self):
+        """Given cells: their scrambling inits [M].  Acquisition: per carrier the (MCC, MNC, colour
+        code) acquired so far, None where no BSCH decoded yet."""
+        if not self.acquire:
+            return self._cells
+        from tetraear.core.etsi import cell_of
+        return [cell_of(v) if a else None for v, a in zip(self.cell_state, self.acquired)]
+
     def reset(self):
         self.tail = np.zeros(0, np.complex64)
         self.y0 = 0                                    # stream position of the buffer's first output
         self.last = np.full(self.M, -(1 << 62), np.int64)   # stream position of each carrier's last frame
+        # acquisition: each carrier's scrambling init (3 = unknown) and whether a CRC-good BSCH was
+        # decoded on it (an all-zero cell has the init of "unknown")
+        self.cell_state = np.full(self.M, 3, np.uint32) if self.acquire else None
+        self.acquired = np.zeros(self.M, bool) if self.acquire else None
+
+    def _decode_buffer(self, buf):
+        kw = {"mac": True} if self.mac else {}
+        if not self.acquire:
+            return self.rx.decode(buf, self._cells, **kw)
+        frames, self.cell_state, ngood = self.rx.decode_acquire(buf, self.cell_state, **kw)
+        self.acquired |= ngood > 0
+        return frames
 
     def decode(self, x):
         """x: the next samples of the capture -> per carrier the frames first decoded now, each with
@@ -275,7 +339,7 @@ class WidebandStream:
         _, n72 = self.rx.plan.lengths(len(buf))
         out = [[] for _ in range(self.M)]
         if n72 >= 16:
-            for k, fr in enumerate(self.rx.decode(buf, self.cells)):
+            for k, fr in enumerate(self._decode_buffer(buf)):
                 for f in fr:
                     a = self.y0 + f["sample"]
                     if a > self.last[k] + self.tol:
@@ -308,7 +372,10 @@ def synth_wideband(Nw, seed=1, snr_db=30.0, cfo_max=300.0, fs=FS_WB, M=M_WB, ove
 class BenchStep:
     """bench.py --chain wideband (C3): one step = the capture's waterfall rows (2048-pt Hann, hop
     2048), channelise the device-resident 20 MSps capture, timing + decision on every (carrier,
-    chunk), lower MAC (sync, Viterbi, CRC) on all of them."""
+    chunk), lower MAC (sync, Viterbi, CRC) on all of them.  TETRA_WB_CELLS=acquire (default
+    "given": every carrier's synthesised cell is configured): the lower MAC acquires each carrier's
+    cell itself over all of its chunks (tetra_lmac_etsi_acquire_groups), the M inits kept on the
+    device from step to step with the context that runs the lower MAC."""
     dtype = "f32 (DSP), int8/int32 (Viterbi)"
 
     def __init__(self, c, Nw, seed, device, snr_db=30.0, fs=FS_WB, M=M_WB):
@@ -332,8 +399,18 @@ class BenchStep:
         c.synchronize()   # torch's ops below need not share the context's stream
         # every chunk of carrier k uses carrier k's scrambling code
         self.cells = cells.repeat_interleave(self.nchunk).contiguous()
+        mode = os.environ.get("TETRA_WB_CELLS", "given")
+        if mode not in ("given", "acquire"):
+            raise ValueError(f"TETRA_WB_CELLS={mode!r}: given or acquire")
+        self.acquire = mode == "acquire"
+        if self.acquire:   # the acquisition state: one init per carrier (3 = unknown), CRC-good BSCH counts
+            self.cells_mode = "acquire"
+            self.cells_true = cells
+            self.cell_state = torch.full((M,), 3, dtype=torch.int32, device=device)
+            self.ngood = torch.zeros(M, dtype=torch.int32, device=device)
         torch.cuda.current_stream(device).synchronize()
-        c.check(c.lib.tetra_etsi_set_cells(c.handle, _hip.ptr(self.cells), self.C), "set_cells")
+        if not self.acquire:
+            c.check(c.lib.tetra_etsi_set_cells(c.handle, _hip.ptr(self.cells), self.C), "set_cells")
         self.y = torch.empty((M, self.ck.rowlen, 2), dtype=torch.float32, device=device)
         # the timing's Oerder-Meyr class sums from the resampler (grouped_om): its group partials
         self.om_grouped = grouped_om(self.plan, self.m2)
@@ -377,7 +454,9 @@ class BenchStep:
         self.s_back = torch.cuda.Stream(device=dev)
         self.back.check(self.back.lib.tetra_set_stream(self.back.handle, ctypes.c_void_p(self.s_back.cuda_stream)),
                         "set_stream")
-        self.back.check(self.back.lib.tetra_etsi_set_cells(self.back.handle, _hip.ptr(self.cells), self.C), "set_cells")
+        if not self.acquire:   # (acquisition: the back context builds its table from the state it is handed)
+            self.back.check(self.back.lib.tetra_etsi_set_cells(self.back.handle, _hip.ptr(self.cells), self.C),
+                            "set_cells")
         self.ys = [self.y, torch.empty_like(self.y)]
         self.oms = [self.om, torch.empty_like(self.om) if self.om is not None else None]
         self.ev_front = [torch.cuda.Event() for _ in range(2)]
@@ -430,6 +509,14 @@ class BenchStep:
                 "etsi_timing_chunks")
 
     def _lmac(self, c):
+        if self.acquire:
+            c.check(c.lib.tetra_lmac_etsi_acquire_groups(c.handle, _hip.ptr(self.soft), _hip.ptr(self.hard),
+                                                         _hip.ptr(self.nsym), self.C, self.sm, self.nchunk,
+                                                         _hip.ptr(self.cell_state), _hip.ptr(self.ngood),
+                                                         _hip.ptr(self.nburst), _hip.ptr(self.bursts),
+                                                         _hip.ptr(self.nblock), _hip.ptr(self.blocks),
+                                                         _hip.ptr(self.type1)), "lmac_etsi_acquire_groups")
+            return
         c.check(c.lib.tetra_lmac_etsi(c.handle, _hip.ptr(self.soft), _hip.ptr(self.hard), _hip.ptr(self.nsym), self.C,
                                       self.sm, _hip.ptr(self.nburst), _hip.ptr(self.bursts), _hip.ptr(self.nblock),
                                       _hip.ptr(self.blocks), _hip.ptr(self.type1)), "lmac_etsi")
@@ -495,7 +582,9 @@ class BenchStep:
                 "timing_chunks_per_carrier": self.nchunk, "timing_chunk_overlap": self.ck.length - self.m2,
                 "parallelism": f"capture-sharded x{world}",
                 "filter_bank": f"D = M / {self.plan.oversample} ({self.fs / self.plan.D / 1e3:g} kHz carriers)",
-                "pipeline": self.pipelined}
+                "pipeline": self.pipelined,
+                # (bench.py adds cells_mode itself only to the config it builds for steps without one)
+                **({"cells": self.cells_mode} if self.acquire else {})}
 
     def realtime_channels(self, value_msps):
         return value_msps * 1e6 / self.fs * self.plan.M   # carriers served at real time
@@ -506,11 +595,13 @@ class BenchStep:
     def quality(self):
         """The last step's decoded work, each burst once (merge_chunks): bursts, blocks, CRC-good
         blocks, and decoded_frac = bursts / the slots on air (M rows of rowlen samples, 1020 per
-        slot; a slot cut by the capture's start or end cannot be decoded, so ~0.97-0.99 is whole)."""
+        slot; a slot cut by the capture's start or end cannot be decoded, so ~0.97-0.99 is whole).
+        TETRA_WB_CELLS=acquire adds cells_acquired: the carriers whose state is the synthesised cell."""
         nb, bursts = self.nburst.cpu().numpy(), self.bursts.cpu().numpy()
         nk, blocks = self.nblock.cpu().numpy(), self.blocks.cpu().numpy()
         keep, kb = merge_chunks(nb, bursts, nk, blocks, self.plan.M, self.nchunk, self.m2)
         slots = self.plan.M * self.ck.rowlen / BURST_SAMPLES
         return dict(blocks=int(kb.sum()), crc_ok=int((blocks[..., 1].astype(bool) & kb).sum()),
                     bursts=int(keep.sum()), decoded_frac=round(float(keep.sum()) / slots, 4),
-                    per_chunk=dict(bursts=int(nb.sum()), blocks=int(nk.sum())))
+                    per_chunk=dict(bursts=int(nb.sum()), blocks=int(nk.sum())),
+                    **({"cells_acquired": int((self.cell_state == self.cells_true).sum())} if self.acquire else {}))
