@@ -572,6 +572,37 @@ int tetra_etsi_mac(tetra_ctx *ctx, const int32_t *nsym, size_t C, const int32_t 
                    const int32_t *nblock, const int32_t *blocks, const uint8_t *type1, tetra_etsi_tdma *tdma,
                    int32_t *slots /*[C][MAXB][4]*/, int32_t *npdu /*[C][MAXJ]*/,
                    int32_t *pdus /*[C][MAXJ][MAXPDU][16]*/);
+/* tetra_etsi_mac over groups of overlapping rows (a new symbol of ABI version 2; nothing existing
+ * changed shape).  Rows g G .. g G + G - 1 are the chunk rows of carrier g in time order, as for
+ * tetra_lmac_etsi_acquire_groups; row i of a group starts row_bits bits after row i - 1 (the wideband
+ * chain: m2 / 2), so consecutive rows may share bursts.  npdu and pdus are tetra_etsi_mac's.  Per
+ * group, the live bursts (row i, burst b < nburst clamped to 0..MAXB) have pos = i row_bits + start
+ * bit (int64) and are taken in the order (pos, row, b):
+ *   keep [C][MAXB]: 1 for the first burst of the order and for every burst whose pos exceeds that of
+ *     the previous burst in the order (kept or not) by more than tol_bits, else 0 -- each burst
+ *     once, the first copy; rows past nburst not written;
+ *   slots [C][MAXB][TETRA_SLOT_FIELDS] and tdma [C / G] (in/out): one timebase per group over all
+ *     live bursts in that order, p = bit0 + pos:
+ *     1. when locked: d = p - anchor_bit, k = floor((d + 255) / 510), r = d - 510 k.  k >=
+ *        TETRA_TDMA_EXPIRE drops the lock; k <= -TETRA_TDMA_EXPIRE predicts nothing and keeps it;
+ *        else |r| <= TETRA_TDMA_TOL predicts slot (anchor_slot + k) mod TETRA_TDMA_SLOTS.  d < 0
+ *        does not drop the lock: a burst's copy in the next row, and every burst of a carried tail,
+ *        sits behind the anchor;
+ *     2. an SB with its own STATUS 0 SYNC (as tetra_etsi_mac's rule 1): its slot, FLAGS bit 0, bit 1
+ *        if the group was locked on entry to this burst and rule 1 predicted another slot or none;
+ *        anchor = (p, slot), locked -- also when p is behind the anchor;
+ *     3. else a predicted burst takes that slot, and the anchor moves to (p, slot) only if k >= 1;
+ *     4. else the row reads 0, 0, 0, 0.
+ *     After the walk bit0 += advance.  Rows past nburst are not written.
+ * 1 <= G <= 64, C % G == 0, row_bits >= 0 and tol_bits >= 0, else TETRA_E_INVALID with nothing
+ * written.  G = 1 on rows of ascending start bits (at least 256 bits apart) with row_bits = 0 and
+ * advance = 2 max(nsym - 1, 0) equals tetra_etsi_mac.  nsym [C] is not read.  Host or device pointers. */
+int tetra_etsi_mac_groups(tetra_ctx *ctx, const int32_t *nsym, size_t C, size_t G, int64_t row_bits,
+                          int64_t tol_bits, int64_t advance, const int32_t *nburst, const int32_t *bursts,
+                          const int32_t *nblock, const int32_t *blocks, const uint8_t *type1,
+                          tetra_etsi_tdma *tdma /*[C/G] in/out*/, int32_t *keep /*[C][MAXB]*/,
+                          int32_t *slots /*[C][MAXB][4]*/, int32_t *npdu /*[C][MAXJ]*/,
+                          int32_t *pdus /*[C][MAXJ][MAXPDU][16]*/);
 
 /* The ETSI receiver's AFC mixer on a streaming window: out [C][N] cf32 = iq (cf32 rows ld samples
  * apart) x exp(-j 2 pi f (n0 + n) / fs), n0 = the window's first sample in the capture (frequency_shift's
@@ -597,6 +628,12 @@ int tetra_etsi_encode_blocks(tetra_ctx *ctx, const uint8_t *type1, size_t F, int
 int tetra_synth_bursts_per_channel(size_t N, double fs);
 int tetra_synth_etsi(tetra_ctx *ctx, size_t C, size_t N, double fs, uint64_t seed, float snr_db, float cfo_max,
                      void *iq, uint32_t *cell_init, int32_t *kinds, uint8_t *payload, double *t0);
+/* Opt-in slot grid (a context flag, default 0: every output bit for bit as without it).  on != 0:
+ * the SYNC PDU of channel ch's burst b carries slot = (tetra_synth_slot0(seed, ch) + b) mod
+ * TETRA_TDMA_SLOTS as TN field = slot % 4 (type-1 bits 10..11), FN = slot / 4 % 18 + 1 (12..16), MN =
+ * slot / 72 + 1 (17..22) in place of random bits, in tetra_synth_etsi and tetra_synth_wideband. */
+int tetra_synth_set_grid(tetra_ctx *ctx, int on);
+int tetra_synth_slot0(uint64_t seed, size_t ch);   /* host only: the slot count of channel ch's burst 0 */
 
 /* ---------------------------------------------------------------- wideband channeliser (C3)
  * A fs = 20 MSps capture -> M carriers at fs/M spacing (polyphase filter bank, D = M/4, rocFFT)

@@ -156,6 +156,8 @@ ProfScope::~ProfScope() {
     c->recs.push_back({name, a, b});
 }
 
+void synth_forget(const tetra_ctx *ctx);   // etsi_synth.hip: drops the context's tetra_synth_set_grid flag
+
 extern "C" {
 
 int tetra_profile(tetra_ctx *ctx, int enable) {
@@ -235,6 +237,7 @@ tetra_ctx *tetra_create(int device) {
 
 void tetra_destroy(tetra_ctx *ctx) {
     if (!ctx) return;
+    synth_forget(ctx);
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     for (auto &r : ctx->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }

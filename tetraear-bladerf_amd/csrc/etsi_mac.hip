@@ -6,6 +6,10 @@
 //               the lane walks its PDUs from that row and writes their records; the group's first
 //               lane then runs the channel's timebase over its bursts, taking a synchronisation
 //               burst's slot count from the lane that parsed its BSCH block (through LDS).
+//   k_mac_walk, k_tdma_groups  (tetra_etsi_mac_groups, restated in tests/_etsi_mac_groups.py): the same
+//               block walk, then per group of overlapping rows -- a wideband carrier's chunks -- one
+//               wave that rank-sorts the group's bursts by position in LDS, keeps each burst once and
+//               runs one timebase over the merged order.
 #include "common.h"
 
 namespace {
@@ -220,20 +224,12 @@ __device__ __forceinline__ void timebase(int nb, const int32_t *__restrict__ bur
     td->locked = locked;
 }
 
-// Grid: 16 lanes per channel, MAC_BLOCK / 16 channels per workgroup; the lanes past C idle.
-__global__ __launch_bounds__(MAC_BLOCK) void k_etsi_mac(int C, const int32_t *__restrict__ nsym,
-                                                        const int32_t *__restrict__ nburst,
-                                                        const int32_t *__restrict__ bursts,
-                                                        const int32_t *__restrict__ nblock,
-                                                        const int32_t *__restrict__ blocks,
-                                                        const uint8_t *__restrict__ type1, tetra_etsi_tdma *tdma,
-                                                        int32_t *__restrict__ slots, int32_t *__restrict__ npdu,
-                                                        int32_t *__restrict__ pdus) {
-    __shared__ uint32_t rows[MAC_BLOCK * WROW];
-    __shared__ int sync_slot[MAC_BLOCK];
-    const int tid = threadIdx.x, j = tid & (MAC_LANES - 1);
-    const long ch = (long)blockIdx.x * (MAC_BLOCK / MAC_LANES) + tid / MAC_LANES;
-    const bool act = ch < C;
+// Lane j of channel ch walks its block j into rows + tid * WROW and writes npdu / pdus; returns the
+// slot count of the block's STATUS 0 SYNC record, -1 where it gave none.  Shared by both kernels.
+__device__ __forceinline__ int walk_block(bool act, long ch, int j, int tid, uint32_t *rows,
+                                          const int32_t *__restrict__ nblock, const int32_t *__restrict__ blocks,
+                                          const uint8_t *__restrict__ type1, int32_t *__restrict__ npdu,
+                                          int32_t *__restrict__ pdus) {
     int own = -1;
     if (act) {
         const size_t cj = (size_t)ch * MAXJ + j;
@@ -264,11 +260,153 @@ __global__ __launch_bounds__(MAC_BLOCK) void k_etsi_mac(int C, const int32_t *__
         }
         npdu[cj] = count;
     }
-    sync_slot[tid] = own;
+    return own;
+}
+
+// Grid: 16 lanes per channel, MAC_BLOCK / 16 channels per workgroup; the lanes past C idle.
+__global__ __launch_bounds__(MAC_BLOCK) void k_etsi_mac(int C, const int32_t *__restrict__ nsym,
+                                                        const int32_t *__restrict__ nburst,
+                                                        const int32_t *__restrict__ bursts,
+                                                        const int32_t *__restrict__ nblock,
+                                                        const int32_t *__restrict__ blocks,
+                                                        const uint8_t *__restrict__ type1, tetra_etsi_tdma *tdma,
+                                                        int32_t *__restrict__ slots, int32_t *__restrict__ npdu,
+                                                        int32_t *__restrict__ pdus) {
+    __shared__ uint32_t rows[MAC_BLOCK * WROW];
+    __shared__ int sync_slot[MAC_BLOCK];
+    const int tid = threadIdx.x, j = tid & (MAC_LANES - 1);
+    const long ch = (long)blockIdx.x * (MAC_BLOCK / MAC_LANES) + tid / MAC_LANES;
+    const bool act = ch < C;
+    sync_slot[tid] = walk_block(act, ch, j, tid, rows, nblock, blocks, type1, npdu, pdus);
     __syncthreads();
     if (act && j == 0)
         timebase(min(max(nburst[ch], 0), MAXB), bursts + (size_t)ch * MAXB * 2, sync_slot + tid, nsym[ch], tdma + ch,
                  slots + (size_t)ch * MAXB * TETRA_SLOT_FIELDS);
+}
+
+// ---------------------------------------------------------------- groups of overlapping rows
+// tetra_etsi_mac_groups: k_etsi_mac's block walk (k_mac_walk: the same lanes, no timebase; lane b < 8
+// of a row leaves burst b's own-SYNC slot count, -1 for none, in own [C][MAXB]), then k_tdma_groups,
+// one wave per group of G rows: merge_chunks and the timebase over the group's bursts in the order
+// (pos, row, b), pos = row * row_bits + start bit.
+constexpr int MAXG = 64, MAXE = MAXG * MAXB;   // rows per group, burst entries per group
+constexpr int64_t K_SPAN = 510 * (int64_t)TETRA_TDMA_EXPIRE - 255;   // d >= K_SPAN: k >= EXPIRE; d < -K_SPAN: k <= -EXPIRE
+
+__global__ __launch_bounds__(MAC_BLOCK) void k_mac_walk(int C, const int32_t *__restrict__ nburst,
+                                                        const int32_t *__restrict__ bursts,
+                                                        const int32_t *__restrict__ nblock,
+                                                        const int32_t *__restrict__ blocks,
+                                                        const uint8_t *__restrict__ type1, int32_t *__restrict__ own,
+                                                        int32_t *__restrict__ npdu, int32_t *__restrict__ pdus) {
+    __shared__ uint32_t rows[MAC_BLOCK * WROW];
+    __shared__ int sync_slot[MAC_BLOCK];
+    const int tid = threadIdx.x, j = tid & (MAC_LANES - 1);
+    const long ch = (long)blockIdx.x * (MAC_BLOCK / MAC_LANES) + tid / MAC_LANES;
+    const bool act = ch < C;
+    sync_slot[tid] = walk_block(act, ch, j, tid, rows, nblock, blocks, type1, npdu, pdus);
+    __syncthreads();
+    if (act && j < min(max(nburst[ch], 0), MAXB)) {   // lane b: the block of burst b by the sync kernel's numbering
+        const int32_t *bu = bursts + (size_t)ch * MAXB * 2;
+        int q = 0;
+        for (int b = 0; b < j; ++b) q += bu[2 * b + 1] == TETRA_NDB_N ? 1 : 2;
+        own[(size_t)ch * MAXB + j] = bu[2 * j + 1] == TETRA_SB && q < MAXJ ? sync_slot[tid - j + q] : -1;
+    }
+}
+
+// One wave per group.  Entry e = row * MAXB + b, so the order (pos, row, b) is (pos, e).
+__global__ __launch_bounds__(64) void k_tdma_groups(int G, int64_t row_bits, int64_t tol_bits, int64_t advance,
+                                                    const int32_t *__restrict__ nburst,
+                                                    const int32_t *__restrict__ bursts,
+                                                    const int32_t *__restrict__ own, tetra_etsi_tdma *tdma,
+                                                    int32_t *__restrict__ keep, int32_t *__restrict__ slots) {
+    __shared__ int64_t pos[MAXE];
+    __shared__ int32_t ownv[MAXE];    // own-SYNC slot count, -1 none, DEAD past the row's nburst
+    __shared__ int32_t res[MAXE];     // by entry: slot | flags << 16, -1 unknown
+    __shared__ uint16_t order[MAXE];  // rank -> entry
+    __shared__ int nlive;
+    constexpr int32_t DEAD = INT32_MIN;
+    const int lane = threadIdx.x, ne = G * MAXB;
+    const size_t c0 = (size_t)blockIdx.x * G;
+    if (lane == 0) nlive = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int e = lane; e < ne; e += 64) {
+        const int i = e / MAXB, b = e % MAXB;
+        const bool live = b < min(max(nburst[c0 + i], 0), MAXB);
+        pos[e] = live ? (int64_t)((uint64_t)i * (uint64_t)row_bits) + bursts[((c0 + i) * MAXB + b) * 2] : 0;
+        ownv[e] = live ? own[(c0 + i) * MAXB + b] : DEAD;
+        mine += live;
+    }
+    if (mine) atomicAdd(&nlive, mine);
+    __syncthreads();
+    for (int e = lane; e < ne; e += 64) {   // rank sort: exact and stable
+        if (ownv[e] == DEAD) continue;
+        const int64_t pe = pos[e];
+        int rank = 0;
+#pragma unroll 8
+        for (int f = 0; f < ne; ++f) {   // ne is a multiple of 8: eight LDS read pairs in flight
+            const int64_t pf = pos[f];
+            rank += (int)(ownv[f] != DEAD) & ((int)(pf < pe) | ((int)(pf == pe) & (int)(f < e)));   // no branches
+        }
+        order[rank] = (uint16_t)e;
+    }
+    __syncthreads();
+    const int n = nlive;
+    for (int r = lane; r < n; r += 64) {   // merge_chunks' chain rule: against the previous in order
+        const int e = order[r];
+        keep[(c0 + e / MAXB) * MAXB + e % MAXB] = r == 0 || pos[e] - pos[order[r - 1]] > tol_bits;
+    }
+    if (lane == 0) {
+        tetra_etsi_tdma *td = tdma + blockIdx.x;
+        const int64_t bit0 = td->bit0;
+        int64_t abit = td->anchor_bit;
+        int aslot = td->anchor_slot;
+        bool locked = td->locked != 0;
+        for (int r = 0; r < n; ++r) {
+            const int e = order[r];
+            const int64_t p = bit0 + pos[e];
+            const bool was = locked;
+            int pred = -1, k = 0;
+            if (locked) {
+                const int64_t d = p - abit;
+                if (d >= K_SPAN) {
+                    locked = false;
+                } else if (d >= -K_SPAN) {
+                    const int x = (int)d + 255;
+                    k = x >= 0 ? x / 510 : -((509 - x) / 510);
+                    const int rr = (int)d - 510 * k;
+                    if (rr >= -TETRA_TDMA_TOL && rr <= TETRA_TDMA_TOL)
+                        pred = (aslot + k + TETRA_TDMA_SLOTS) % TETRA_TDMA_SLOTS;
+                }
+            }
+            const int mine_slot = ownv[e];
+            int out = pred;
+            if (mine_slot >= 0) {
+                out = mine_slot | (1 | (was && pred != mine_slot ? 2 : 0)) << 16;
+                abit = p;
+                aslot = mine_slot;
+                locked = true;
+            } else if (pred >= 0 && k >= 1) {
+                abit = p;
+                aslot = pred;
+            }
+            res[e] = out;
+        }
+        td->bit0 = bit0 + advance;
+        td->anchor_bit = abit;
+        td->anchor_slot = aslot;
+        td->locked = locked;
+    }
+    __syncthreads();
+    for (int e = lane; e < ne; e += 64) {
+        if (ownv[e] == DEAD) continue;
+        const int v = res[e], slot = v & 0xffff;
+        int32_t *row = slots + ((c0 + e / MAXB) * MAXB + e % MAXB) * TETRA_SLOT_FIELDS;
+        row[TETRA_SLOT_TN] = v >= 0 ? slot % 4 + 1 : 0;
+        row[TETRA_SLOT_FN] = v >= 0 ? slot / 4 % 18 + 1 : 0;
+        row[TETRA_SLOT_MN] = v >= 0 ? slot / 72 + 1 : 0;
+        row[TETRA_SLOT_FLAGS] = v >= 0 ? v >> 16 : 0;
+    }
 }
 
 }  // namespace
@@ -299,6 +437,46 @@ extern "C" int tetra_etsi_mac(tetra_ctx *ctx, const int32_t *nsym, size_t C, con
         PROF(ctx, "etsi_mac");
         hipLaunchKernelGGL(k_etsi_mac, dim3(grid_for(C * MAC_LANES, MAC_BLOCK)), dim3(MAC_BLOCK), 0, ctx->stream, (int)C,
                            ns, nb, bu, nk, bk, t1, td, so, np, po);
+    }
+    return st.finish();
+}
+
+extern "C" int tetra_etsi_mac_groups(tetra_ctx *ctx, const int32_t *nsym, size_t C, size_t G, int64_t row_bits,
+                                     int64_t tol_bits, int64_t advance, const int32_t *nburst, const int32_t *bursts,
+                                     const int32_t *nblock, const int32_t *blocks, const uint8_t *type1,
+                                     tetra_etsi_tdma *tdma, int32_t *keep, int32_t *slots, int32_t *npdu,
+                                     int32_t *pdus) {
+    if (!ctx) return TETRA_E_INVALID;
+    if (C == 0 || !nsym || !nburst || !bursts || !nblock || !blocks || !type1 || !tdma || !keep || !slots || !npdu ||
+        !pdus)
+        return tetra_fail(ctx, TETRA_E_INVALID, "tetra_etsi_mac_groups: C > 0 and every array");
+    if (G < 1 || G > (size_t)MAXG || C % G != 0 || row_bits < 0 || tol_bits < 0)
+        return tetra_fail(ctx, TETRA_E_INVALID,
+                          "tetra_etsi_mac_groups: 1 <= G <= %d rows per group dividing C, row_bits and tol_bits >= 0 "
+                          "(C %zu, G %zu, row_bits %lld, tol_bits %lld)", MAXG, C, G, (long long)row_bits,
+                          (long long)tol_bits);
+    if (C > ((size_t)1 << 24)) return tetra_fail(ctx, TETRA_E_INVALID, "too many rows for one tetra_etsi_mac_groups call (%zu)", C);
+    const size_t NG = C / G;
+    Staging st(ctx);
+    const int32_t *nb = (const int32_t *)st.in(nburst, C * 4);
+    const int32_t *bu = (const int32_t *)st.in(bursts, C * MAXB * 2 * 4);
+    const int32_t *nk = (const int32_t *)st.in(nblock, C * 4);
+    const int32_t *bk = (const int32_t *)st.in(blocks, C * MAXJ * 4 * 4);
+    const uint8_t *t1 = (const uint8_t *)st.in(type1, C * MAXJ * 268);
+    tetra_etsi_tdma *td = (tetra_etsi_tdma *)st.inout(tdma, NG * sizeof(tetra_etsi_tdma));
+    // in/out: what the kernels do not write keeps the caller's contents in host memory too
+    int32_t *kp = (int32_t *)st.inout(keep, C * MAXB * 4);
+    int32_t *so = (int32_t *)st.inout(slots, C * MAXB * TETRA_SLOT_FIELDS * 4);
+    int32_t *np = (int32_t *)st.out(npdu, C * MAXJ * 4);
+    int32_t *po = (int32_t *)st.inout(pdus, C * MAXJ * MAXPDU * NF * 4);
+    int32_t *own = (int32_t *)ws(ctx, S_W0, C * MAXB * 4);
+    if (!nb || !bu || !nk || !bk || !t1 || !td || !kp || !so || !np || !po || !own) return st.finish();
+    {
+        PROF(ctx, "etsi_mac_groups");
+        hipLaunchKernelGGL(k_mac_walk, dim3(grid_for(C * MAC_LANES, MAC_BLOCK)), dim3(MAC_BLOCK), 0, ctx->stream, (int)C,
+                           nb, bu, nk, bk, t1, own, np, po);
+        hipLaunchKernelGGL(k_tdma_groups, dim3((unsigned)NG), dim3(64), 0, ctx->stream, (int)G, row_bits, tol_bits,
+                           advance, nb, bu, own, td, kp, so);
     }
     return st.finish();
 }

@@ -9,6 +9,9 @@
 // Used by bench.py (data generated in HBM, never crossing PCIe) and by the GPU tests.
 #include "common.h"
 
+#include <mutex>
+#include <unordered_set>
+
 namespace {
 
 constexpr int SPAN = 6;
@@ -23,6 +26,12 @@ __host__ __device__ inline uint64_t mix64(uint64_t x) {
 }
 __device__ inline uint64_t hkey(uint64_t seed, uint64_t a, uint64_t b, uint64_t c) {
     return mix64(seed ^ mix64(a * 0x9E3779B97F4A7C15ull ^ mix64(b * 0xD1B54A32D192ED03ull ^ c)));
+}
+// Per-channel identity hash (cell, start time) and, from it, the slot count of the channel's burst 0
+// on the opt-in slot grid (tetra_synth_set_grid).
+__host__ __device__ inline uint64_t chan_hash(uint64_t seed, uint64_t ch) { return mix64(seed * 0x9E3779B97F4A7C15ull + ch); }
+__host__ __device__ inline int slot0_of(uint64_t seed, uint64_t ch) {
+    return (int)(mix64(chan_hash(seed, ch) ^ 0x5107ull) % TETRA_TDMA_SLOTS);
 }
 __device__ inline float u01(uint64_t h) { return (float)((h >> 40) + 0.5) * (1.0f / 16777216.0f); }
 
@@ -77,7 +86,8 @@ __device__ void encode_into(const uint8_t *t1, int kind, const uint8_t *scr, uin
 __global__ __launch_bounds__(64) void k_synth_bursts(uint64_t seed, int NBR, const uint8_t *__restrict__ cell_scr,
                                                      const uint8_t *__restrict__ bsch_scr,
                                                      const uint32_t *__restrict__ cell_init, uint8_t *__restrict__ bits,
-                                                     int32_t *__restrict__ kinds, uint8_t *__restrict__ payload) {
+                                                     int32_t *__restrict__ kinds, uint8_t *__restrict__ payload,
+                                                     int grid) {
     const int ch = blockIdx.x / NBR, b = blockIdx.x % NBR, lane = threadIdx.x;
     __shared__ uint8_t t1[2][268];
     __shared__ uint8_t t2s[288];
@@ -98,11 +108,15 @@ __global__ __launch_bounds__(64) void k_synth_bursts(uint64_t seed, int NBR, con
         // BSCH: the SYNC PDU of the channel's cell -- MAC-SYNC colour code at bits 4..9 and
         // D-MLE-SYNC MCC 31..40 / MNC 41..54 (EN 300 392-2 §21.4.4.2, §18.4.2.1), MSB first
         const uint32_t ecc = cell_init[ch] >> 2;   // MCC(10) MNC(14) CC(6)
+        // slot grid (opt-in): TN 10..11, FN 12..16, MN 17..22 of burst b's slot count
+        const int slot = grid ? (slot0_of(seed, ch) + b) % TETRA_TDMA_SLOTS : 0;
+        const uint32_t tfm = (uint32_t)(slot % 4) << 11 | (uint32_t)(slot / 4 % 18 + 1) << 6 | (uint32_t)(slot / 72 + 1);
         for (int i = lane; i < 268; i += 64) {
             uint8_t v = i < n1 ? (uint8_t)(hkey(seed, ch, b * 2 + blk, i) & 1) : 0;
             if (kind == 2 && i >= 4 && i < 10) v = (uint8_t)((ecc >> (9 - i)) & 1u);          // CC
             if (kind == 2 && i >= 31 && i < 41) v = (uint8_t)((ecc >> (29 - (i - 31))) & 1u);  // MCC
             if (kind == 2 && i >= 41 && i < 55) v = (uint8_t)((ecc >> (19 - (i - 41))) & 1u);  // MNC
+            if (grid && kind == 2 && i >= 10 && i < 23) v = (uint8_t)((tfm >> (22 - i)) & 1u);       // TN FN MN
             t1[blk][i] = v;
             pl[i] = v;
         }
@@ -209,6 +223,10 @@ __global__ __launch_bounds__(256) void k_synth_iq(const uint8_t *__restrict__ ph
     iq[gid] = make_float2(yr, yi);
 }
 
+// Contexts whose synthesiser plants the slot grid (tetra_synth_set_grid); tetra_destroy forgets one.
+std::mutex g_grid_mu;
+std::unordered_set<const tetra_ctx *> g_grid_on;
+
 void lfsr(uint32_t r, int n, uint8_t *out) {
     for (int i = 0; i < n; ++i) {
         const uint32_t b = ((r >> 0) ^ (r >> 6) ^ (r >> 9) ^ (r >> 10) ^ (r >> 16) ^ (r >> 20) ^ (r >> 21) ^ (r >> 22) ^
@@ -220,7 +238,22 @@ void lfsr(uint32_t r, int n, uint8_t *out) {
 
 }  // namespace
 
+void synth_forget(const tetra_ctx *ctx) {
+    std::lock_guard<std::mutex> lk(g_grid_mu);
+    g_grid_on.erase(ctx);
+}
+
 extern "C" {
+
+int tetra_synth_set_grid(tetra_ctx *ctx, int on) {
+    if (!ctx) return TETRA_E_INVALID;
+    std::lock_guard<std::mutex> lk(g_grid_mu);
+    if (on) g_grid_on.insert(ctx);
+    else g_grid_on.erase(ctx);
+    return TETRA_OK;
+}
+
+int tetra_synth_slot0(uint64_t seed, size_t ch) { return slot0_of(seed, ch); }
 
 int tetra_synth_bursts_per_channel(size_t N, double fs) {
     const double syms = (double)N * 18000.0 / fs;
@@ -237,7 +270,7 @@ int tetra_synth_etsi(tetra_ctx *ctx, size_t C, size_t N, double fs, uint64_t see
     std::vector<double> t0h(C);
     std::vector<uint8_t> tab(C * 432 + 432);
     for (size_t c = 0; c < C; ++c) {
-        const uint64_t h = mix64(seed * 0x9E3779B97F4A7C15ull + c);
+        const uint64_t h = chan_hash(seed, c);
         const uint32_t mcc = (uint32_t)(h & 0x3FF), mnc = (uint32_t)((h >> 10) & 0x3FFF), cc = (uint32_t)((h >> 24) & 0x3F);
         init[c] = ((((mcc & 0x3FFu) << 20) | ((mnc & 0x3FFFu) << 6) | (cc & 0x3Fu)) << 2) | 3u;
         t0h[c] = 8.0 + 255.0 * ((double)((h >> 32) & 0xFFFF) / 65536.0) + ((double)((h >> 48) & 0xFFF) / 4096.0);
@@ -257,11 +290,16 @@ int tetra_synth_etsi(tetra_ctx *ctx, size_t C, size_t N, double fs, uint64_t see
     HIP_TRY(ctx, hipMemcpyAsync(scr, tab.data(), tab.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ci, init.data(), C * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(tt, t0h.data(), C * 8, hipMemcpyHostToDevice, ctx->stream));
+    int grid;
+    {
+        std::lock_guard<std::mutex> lk(g_grid_mu);
+        grid = (int)g_grid_on.count(ctx);
+    }
     const float amp = 0.5f;
     const float sigma = snr_db > -100.f && snr_db < 200.f
                             ? amp * sqrtf((float)(fs / 18000.0) / powf(10.f, snr_db / 10.f) / 2.f) : 0.f;
     hipLaunchKernelGGL(k_synth_bursts, dim3((unsigned)(C * NBR)), dim3(64), 0, ctx->stream, seed, NBR, scr,
-                       scr + C * 432, ci, bits, kd, pl);
+                       scr + C * 432, ci, bits, kd, pl, grid);
     hipLaunchKernelGGL(k_synth_phase, dim3((unsigned)C), dim3(64), 0, ctx->stream, bits, nsym, ph, seed);
     hipLaunchKernelGGL(k_synth_iq, dim3(grid_for(C * N, 256)), dim3(256), 0, ctx->stream, ph, nsym, (long)N, fs, seed,
                        amp, sigma, cfo_max, tt, x);

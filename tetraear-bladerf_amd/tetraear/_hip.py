@@ -148,6 +148,8 @@ def _bind(L):
                                            _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]),
         "tetra_lmac_etsi_stream": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "tetra_etsi_mac": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "tetra_etsi_mac_groups": (_i32, [_vp, _vp, _sz, _sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "tetra_etsi_mix": (_i32, [_vp, _vp, _sz, _sz, _sz, _vp, ctypes.c_double, ctypes.c_int64, _vp]),
         "tetra_etsi_decode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
         "tetra_etsi_encode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp]),
@@ -163,6 +165,8 @@ def _bind(L):
         "tetra_synth_wideband": (_i32, [_vp, ctypes.POINTER(WbPlan), _sz, ctypes.c_uint64, ctypes.c_float,
                                         ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
         "tetra_synth_bursts_per_channel": (_i32, [_sz, ctypes.c_double]),
+        "tetra_synth_set_grid": (_i32, [_vp, _i32]),
+        "tetra_synth_slot0": (_i32, [ctypes.c_uint64, _sz]),
         "tetra_synth_etsi": (_i32, [_vp, _sz, _sz, ctypes.c_double, ctypes.c_uint64, ctypes.c_float, ctypes.c_float,
                                     _vp, _vp, _vp, _vp, _vp]),
     }

@@ -208,16 +208,21 @@ class WidebandReceiver:
                 ns.reshape(M, ck.nchunk))
 
 
-    def decode(self, x, cells, mac=False):
+    def decode(self, x, cells, mac=False, timebase=False, tol=64):
         """x [Nw] -> per carrier the frames decoded from it, each burst once (merge_chunks), in row
         order: demod, then the ETSI lower MAC on every (carrier, chunk) with carrier k's scrambling
         init cells[k].  A frame is the lower MAC's dict (core/etsi.py) plus "chunk" and "sample" (its
         start in the carrier's 72 kHz row, to within the timing phase).  mac=True: every block gains
         ``npdu`` / ``pdus`` (tetra_etsi_mac's PDU walk, per block; the frames get no tn / fn / mn --
-        a timebase over overlapping chunk rows needs the rows' bursts merged first)."""
-        return self._decode(x, np.asarray(cells, np.uint32), None, mac)[0]
+        that takes timebase=True).  timebase=True (implies the PDU walk): tetra_etsi_mac_groups merges
+        each carrier's chunk rows on the device (its keep replaces merge_chunks') and runs one TDMA
+        timebase per carrier over them, a new stream per call: every frame gains ``tn`` / ``fn`` /
+        ``mn`` / ``slot_flags`` as EtsiLowerMac's frames carry them (None before the carrier's first
+        CRC-good SYNC).  tol: the duplicate distance in 72 kHz samples (merge_chunks'); timebase=True
+        needs it and m2 even (the device works in bits), else ValueError."""
+        return self._decode(x, np.asarray(cells, np.uint32), None, mac, timebase, tol)[0]
 
-    def decode_acquire(self, x, cell_init, mac=False):
+    def decode_acquire(self, x, cell_init, mac=False, timebase=False, tol=64):
         """decode without given cells: cell_init [M] holds each carrier's scrambling init before the
         capture (3 = unknown); every carrier's cell comes from the last CRC-good BSCH over all of its
         chunk rows, and all of its rows are descrambled with it (tetra_lmac_etsi_acquire_groups, G =
@@ -226,13 +231,16 @@ class WidebandReceiver:
         state = np.array(cell_init, np.uint32)
         if state.shape != (self.plan.M,):
             raise ValueError(f"cell_init holds {state.shape} inits, the receiver has {self.plan.M} carriers")
-        frames, ngood = self._decode(x, None, state, mac)
+        frames, ngood = self._decode(x, None, state, mac, timebase, tol)
         return frames, state, ngood
 
-    def _decode(self, x, cells, state, mac):
+    def _decode(self, x, cells, state, mac, timebase=False, tol=64, tdma=None, advance=0):
         """The chain behind decode (cells [M]) and decode_acquire (state [M], updated in place):
-        (frames, ngood or None)."""
+        (frames, ngood or None).  timebase: tdma [M] ETSI_TDMA (in/out; None: new streams), whose bit0
+        moves on by ``advance`` bits after the call (WidebandStream)."""
         from tetraear.core.etsi import EtsiLowerMac
+        if timebase and (self.m2 % 2 or tol % 2 or tol < 0):
+            raise ValueError(f"timebase=True works in bits: m2 ({self.m2}) and tol ({tol}) must be even")
         hard, soft, _, ns = self.demod(x)
         M, nchunk, sm = hard.shape
         C = M * nchunk
@@ -253,13 +261,26 @@ class WidebandReceiver:
             ngood = np.zeros(M, np.int32)
             c.check(c.lib.tetra_lmac_etsi_acquire_groups(c.handle, *rows, nchunk, _hip.ptr(state), _hip.ptr(ngood),
                                                          *outs), "tetra_lmac_etsi_acquire_groups")
-        keep, _ = merge_chunks(nb, bursts, nk, blocks, M, nchunk, self.m2)
         pdus = None
-        if mac:   # the PDU walk is per block; a fresh timebase per row, its slots not reported
+        if timebase:   # merge and timebase per carrier on the device
+            tdma = np.zeros(M, _hip.ETSI_TDMA) if tdma is None else tdma
+            keep = np.zeros((C, _hip.ETSI_MAXB), np.int32)
+            slots = np.zeros((C, _hip.ETSI_MAXB, _hip.SLOT_FIELDS), np.int32)
+            npdu = np.zeros((C, _hip.ETSI_MAXJ), np.int32)
+            recs = np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.PDU_FIELDS), np.int32)
+            c.check(c.lib.tetra_etsi_mac_groups(c.handle, _hip.ptr(np.ascontiguousarray(ns.reshape(-1))), C, nchunk,
+                                                self.m2 // 2, tol // 2, advance, *outs[:4], _hip.ptr(t1),
+                                                _hip.ptr(tdma), _hip.ptr(keep), _hip.ptr(slots), _hip.ptr(npdu),
+                                                _hip.ptr(recs)), "tetra_etsi_mac_groups")
+            keep = keep.astype(bool)
+            pdus = (slots, npdu, recs)
+        else:
+            keep, _ = merge_chunks(nb, bursts, nk, blocks, M, nchunk, self.m2, tol)
+        if mac and not timebase:   # the PDU walk is per block; a fresh timebase per row, its slots not reported
             pdus = EtsiLowerMac(mac=True)._run_mac(c, C, np.ascontiguousarray(ns.reshape(-1)), nb, bursts, nk, blocks,
                                                   t1, None)
         frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1, pdus)
-        if mac:
+        if mac and not timebase:
             for fr in frames:
                 for f in fr:
                     for key in ("tn", "fn", "mn", "slot_flags"):
@@ -294,12 +315,17 @@ class WidebandStream:
     clears them) and read as ``cells``: per carrier (MCC, MNC, colour code), None before the first
     BSCH -- EtsiLowerMac.cells per carrier.  A burst is reported once, as first decoded: one that a
     buffer decoded before its carrier's cell was known is not reported again from the next buffer.
-    ``mac=True``: the blocks carry ``npdu`` / ``pdus`` (WidebandReceiver.decode)."""
+    ``mac=True``: the blocks carry ``npdu`` / ``pdus`` (WidebandReceiver.decode).  ``timebase=True``
+    (implies it): the frames carry ``tn`` / ``fn`` / ``mn`` / ``slot_flags`` from one TDMA timebase per
+    carrier, carried from piece to piece in ``tdma`` [M] (reset() clears it): a buffer's carried tail
+    is decoded again behind the anchor, which places those bursts without moving it."""
     CARRY_Y = 2 * BURST_SAMPLES
 
-    def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False):
+    def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False, timebase=False):
         self.rx = WidebandReceiver(fs, M, m2, oversample)
-        self.acquire, self.mac = cells is None, bool(mac)
+        self.acquire, self.mac, self.timebase = cells is None, bool(mac), bool(timebase)
+        if self.timebase and m2 % 2:
+            raise ValueError(f"timebase=True works in bits: m2 ({m2}) must be even")
         self._cells = None if self.acquire else np.ascontiguousarray(cells, np.uint32)
         p = self.rx.plan
         blocks = int(np.lcm(p.c.down, p.oversample))   # filter-bank blocks per period
@@ -323,8 +349,17 @@ class WidebandStream:
         # decoded on it (an all-zero cell has the init of "unknown")
         self.cell_state = np.full(self.M, 3, np.uint32) if self.acquire else None
         self.acquired = np.zeros(self.M, bool) if self.acquire else None
+        # timebase: each carrier's tetra_etsi_tdma; bit0 = the stream bit of the buffer's first output
+        self.tdma = np.zeros(self.M, _hip.ETSI_TDMA) if self.timebase else None
 
-    def _decode_buffer(self, buf):
+    def _decode_buffer(self, buf, advance=0):
+        if self.timebase:
+            state = np.array(self.cell_state, np.uint32) if self.acquire else None
+            frames, ngood = self.rx._decode(buf, self._cells, state, True, True, 64, self.tdma, advance)
+            if self.acquire:
+                self.cell_state = state
+                self.acquired |= ngood > 0
+            return frames
         kw = {"mac": True} if self.mac else {}
         if not self.acquire:
             return self.rx.decode(buf, self._cells, **kw)
@@ -338,23 +373,36 @@ class WidebandStream:
         buf = np.concatenate([self.tail, np.asarray(x, np.complex64)])
         _, n72 = self.rx.plan.lengths(len(buf))
         out = [[] for _ in range(self.M)]
+        T = max(0, (n72 - self.CARRY_Y) // self.ups) * self.per   # the next buffer starts here
+        dy = self.ups * (T // self.per)                            # ... this many 72 kHz outputs on
+        assert not self.timebase or dy % 2 == 0, "a buffer starts a whole number of bits after the previous one"
+        if n72 < 16 and self.timebase:
+            self.tdma["bit0"] += dy // 2
         if n72 >= 16:
-            for k, fr in enumerate(self._decode_buffer(buf)):
+            for k, fr in enumerate(self._decode_buffer(buf, dy // 2)):
                 for f in fr:
                     a = self.y0 + f["sample"]
                     if a > self.last[k] + self.tol:
                         f["stream_sample"] = int(a)
                         out[k].append(f)
                         self.last[k] = a
-        T = max(0, (n72 - self.CARRY_Y) // self.ups) * self.per   # the next buffer starts here
         self.tail = buf[T:]
-        self.y0 += self.ups * (T // self.per)
+        self.y0 += dy
         return out
 
 
-def synth_wideband(Nw, seed=1, snr_db=30.0, cfo_max=300.0, fs=FS_WB, M=M_WB, oversample=None):
+def planted_slots(seed, M, nb):
+    """[M, nb] slot counts the synthesiser's slot grid (tetra_synth_set_grid) plants: carrier k's burst
+    b carries (tetra_synth_slot0(seed, k) + b) mod 4320 in its SYNC PDU, when it is an SB."""
+    L = _hip.lib()
+    s0 = np.array([L.tetra_synth_slot0(seed, k) for k in range(M)], np.int64)
+    return (s0[:, None] + np.arange(nb)[None, :]) % _hip.TDMA_SLOTS
+
+
+def synth_wideband(Nw, seed=1, snr_db=30.0, cfo_max=300.0, fs=FS_WB, M=M_WB, oversample=None, grid=False):
     """Synthetic capture (device-generated, copied to the host): x [Nw] complex64, cells [M],
-    kinds [M][NB], payload [M][NB][2][268], t0 [M] (carrier k is FFT bin k, at +k fs/M)."""
+    kinds [M][NB], payload [M][NB][2][268], t0 [M] (carrier k is FFT bin k, at +k fs/M).  grid=True:
+    the SBs' SYNC PDUs carry consecutive slot counts (planted_slots) instead of random TN / FN / MN."""
     plan = wb_plan(fs, M, oversample)
     c = _hip.ctx()
     nbb = Nw // plan.D + 1
@@ -364,8 +412,14 @@ def synth_wideband(Nw, seed=1, snr_db=30.0, cfo_max=300.0, fs=FS_WB, M=M_WB, ove
     kinds = np.empty((M, nb), np.int32)
     payload = np.empty((M, nb, 2, 268), np.uint8)
     t0 = np.empty(M, np.float64)
-    c.check(c.lib.tetra_synth_wideband(c.handle, plan.c, Nw, seed, snr_db, cfo_max, _hip.ptr(x), _hip.ptr(cells),
-                                       _hip.ptr(kinds), _hip.ptr(payload), _hip.ptr(t0)), "synth_wideband")
+    if grid:
+        c.check(c.lib.tetra_synth_set_grid(c.handle, 1), "synth_set_grid")
+    try:
+        c.check(c.lib.tetra_synth_wideband(c.handle, plan.c, Nw, seed, snr_db, cfo_max, _hip.ptr(x), _hip.ptr(cells),
+                                           _hip.ptr(kinds), _hip.ptr(payload), _hip.ptr(t0)), "synth_wideband")
+    finally:
+        if grid:
+            c.check(c.lib.tetra_synth_set_grid(c.handle, 0), "synth_set_grid")
     return x, cells, kinds, payload, t0
 
 
@@ -375,7 +429,10 @@ class BenchStep:
     chunk), lower MAC (sync, Viterbi, CRC) on all of them.  TETRA_WB_CELLS=acquire (default
     "given": every carrier's synthesised cell is configured): the lower MAC acquires each carrier's
     cell itself over all of its chunks (tetra_lmac_etsi_acquire_groups), the M inits kept on the
-    device from step to step with the context that runs the lower MAC."""
+    device from step to step with the context that runs the lower MAC.  TETRA_WB_MAC=timebase: the
+    capture is synthesised on the slot grid and tetra_etsi_mac_groups follows the lower MAC on the same
+    context (PDU headers, the merge of each carrier's chunk rows, one TDMA timebase per carrier resident
+    on the device; every step decodes the same capture, so bit0 does not advance)."""
     dtype = "f32 (DSP), int8/int32 (Viterbi)"
 
     def __init__(self, c, Nw, seed, device, snr_db=30.0, fs=FS_WB, M=M_WB):
@@ -393,9 +450,17 @@ class BenchStep:
         cells = torch.empty(M, dtype=torch.int32, device=device)
         self.kinds = torch.empty((M, nb), dtype=torch.int32, device=device)
         self.payload = torch.empty((M, nb, 2, 268), dtype=torch.uint8, device=device)
+        mac = os.environ.get("TETRA_WB_MAC", "")
+        if mac not in ("", "timebase"):
+            raise ValueError(f"TETRA_WB_MAC={mac!r}: timebase, or unset")
+        self.timebase, self.seed = mac == "timebase", seed
+        if self.timebase:
+            c.check(c.lib.tetra_synth_set_grid(c.handle, 1), "synth_set_grid")
         c.check(c.lib.tetra_synth_wideband(c.handle, self.plan.c, Nw, seed, snr_db, 300.0, _hip.ptr(self.x),
                                            _hip.ptr(cells), _hip.ptr(self.kinds), _hip.ptr(self.payload), None),
                 "synth_wideband")
+        if self.timebase:
+            c.check(c.lib.tetra_synth_set_grid(c.handle, 0), "synth_set_grid")
         c.synchronize()   # torch's ops below need not share the context's stream
         # every chunk of carrier k uses carrier k's scrambling code
         self.cells = cells.repeat_interleave(self.nchunk).contiguous()
@@ -425,6 +490,16 @@ class BenchStep:
         self.nblock = torch.empty(self.C, dtype=torch.int32, device=device)
         self.blocks = torch.empty((self.C, _hip.ETSI_MAXJ, 4), dtype=torch.int32, device=device)
         self.type1 = torch.empty((self.C, _hip.ETSI_MAXJ, 268), dtype=torch.uint8, device=device)
+        if self.timebase:
+            if self.m2 % 2:
+                raise ValueError(f"TETRA_WB_MAC=timebase works in bits: m2 ({self.m2}) must be even")
+            self.tdma = torch.zeros((M, 3), dtype=torch.int64, device=device)   # struct tetra_etsi_tdma per carrier
+            self.keep = torch.zeros((self.C, _hip.ETSI_MAXB), dtype=torch.int32, device=device)
+            self.slots = torch.zeros((self.C, _hip.ETSI_MAXB, _hip.SLOT_FIELDS), dtype=torch.int32, device=device)
+            self.npdu = torch.zeros((self.C, _hip.ETSI_MAXJ), dtype=torch.int32, device=device)
+            self.pdus = torch.zeros((self.C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.PDU_FIELDS), dtype=torch.int32,
+                                    device=device)
+            torch.cuda.current_stream(device).synchronize()
         self.nfr = Nw // 2048   # waterfall rows of the capture (2048-pt Hann frames, hop 2048)
         self.wf = torch.empty((self.nfr, 2048), dtype=torch.float32, device=device)
         self.pipelined = False
@@ -508,7 +583,19 @@ class BenchStep:
                                                _hip.ptr(self.hard), _hip.ptr(self.nsym), self.sm, None),
                 "etsi_timing_chunks")
 
+    def _mac(self, c):
+        c.check(c.lib.tetra_etsi_mac_groups(c.handle, _hip.ptr(self.nsym), self.C, self.nchunk, self.m2 // 2, 32, 0,
+                                            _hip.ptr(self.nburst), _hip.ptr(self.bursts), _hip.ptr(self.nblock),
+                                            _hip.ptr(self.blocks), _hip.ptr(self.type1), _hip.ptr(self.tdma),
+                                            _hip.ptr(self.keep), _hip.ptr(self.slots), _hip.ptr(self.npdu),
+                                            _hip.ptr(self.pdus)), "etsi_mac_groups")
+
     def _lmac(self, c):
+        self._lmac_rows(c)
+        if self.timebase:
+            self._mac(c)
+
+    def _lmac_rows(self, c):
         if self.acquire:
             c.check(c.lib.tetra_lmac_etsi_acquire_groups(c.handle, _hip.ptr(self.soft), _hip.ptr(self.hard),
                                                          _hip.ptr(self.nsym), self.C, self.sm, self.nchunk,
@@ -584,7 +671,8 @@ class BenchStep:
                 "filter_bank": f"D = M / {self.plan.oversample} ({self.fs / self.plan.D / 1e3:g} kHz carriers)",
                 "pipeline": self.pipelined,
                 # (bench.py adds cells_mode itself only to the config it builds for steps without one)
-                **({"cells": self.cells_mode} if self.acquire else {})}
+                **({"cells": self.cells_mode} if self.acquire else {}),
+                **({"mac": "timebase"} if self.timebase else {})}
 
     def realtime_channels(self, value_msps):
         return value_msps * 1e6 / self.fs * self.plan.M   # carriers served at real time
@@ -596,12 +684,44 @@ class BenchStep:
         """The last step's decoded work, each burst once (merge_chunks): bursts, blocks, CRC-good
         blocks, and decoded_frac = bursts / the slots on air (M rows of rowlen samples, 1020 per
         slot; a slot cut by the capture's start or end cannot be decoded, so ~0.97-0.99 is whole).
-        TETRA_WB_CELLS=acquire adds cells_acquired: the carriers whose state is the synthesised cell."""
+        TETRA_WB_CELLS=acquire adds cells_acquired: the carriers whose state is the synthesised cell.
+        TETRA_WB_MAC=timebase adds timebase_known, the share of kept bursts with a slot (tn != 0), and
+        timebase_wrong, the kept, known bursts whose slot is not the planted one (a burst is matched
+        to its planted one by its first block's type-1 bits, so only CRC-good ones are judged;
+        timebase_checked counts them)."""
         nb, bursts = self.nburst.cpu().numpy(), self.bursts.cpu().numpy()
         nk, blocks = self.nblock.cpu().numpy(), self.blocks.cpu().numpy()
         keep, kb = merge_chunks(nb, bursts, nk, blocks, self.plan.M, self.nchunk, self.m2)
+        tb = {}
+        if self.timebase:
+            dkeep = self.keep.cpu().numpy().astype(bool) & (np.arange(keep.shape[1])[None, :] < nb[:, None])
+            if not np.array_equal(dkeep, keep):
+                raise RuntimeError("tetra_etsi_mac_groups' keep differs from merge_chunks'")
+            tb = self._timebase_quality(keep, nk, blocks)
         slots = self.plan.M * self.ck.rowlen / BURST_SAMPLES
         return dict(blocks=int(kb.sum()), crc_ok=int((blocks[..., 1].astype(bool) & kb).sum()),
                     bursts=int(keep.sum()), decoded_frac=round(float(keep.sum()) / slots, 4),
                     per_chunk=dict(bursts=int(nb.sum()), blocks=int(nk.sum())),
-                    **({"cells_acquired": int((self.cell_state == self.cells_true).sum())} if self.acquire else {}))
+                    **({"cells_acquired": int((self.cell_state == self.cells_true).sum())} if self.acquire else {}),
+                    **tb)
+
+    def _timebase_quality(self, keep, nk, blocks):
+        slots, t1 = self.slots.cpu().numpy(), self.type1.cpu().numpy()
+        kinds, payload = self.kinds.cpu().numpy(), self.payload.cpu().numpy()
+        planted = planted_slots(self.seed, self.plan.M, kinds.shape[1])
+        known = slots[..., 0] != 0
+        wrong = checked = 0
+        for ch, b in zip(*np.nonzero(keep & known)):
+            k = ch // self.nchunk
+            j = next((j for j in range(min(int(nk[ch]), _hip.ETSI_MAXJ)) if blocks[ch, j, 2] == b and blocks[ch, j, 3] == 0), None)
+            if j is None or not blocks[ch, j, 1]:
+                continue
+            n1 = (268, 124, 60)[int(blocks[ch, j, 0])]
+            hit = np.nonzero((payload[k, :, 0, :n1] == (t1[ch, j, :n1] & 1)).all(axis=1))[0]
+            if len(hit) != 1:
+                continue
+            s = int(planted[k, hit[0]])
+            checked += 1
+            wrong += slots[ch, b, :3].tolist() != [s % 4 + 1, s // 4 % 18 + 1, s // 72 + 1]
+        return dict(timebase_known=round(float((keep & known).sum()) / max(int(keep.sum()), 1), 4),
+                    timebase_wrong=int(wrong), timebase_checked=int(checked))
