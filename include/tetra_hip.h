@@ -43,7 +43,9 @@ enum {
 };
 
 /* Sample formats of input arrays.  TETRA_SC16: interleaved int16 (I, Q), the BladeRF wire format,
- * scaled by 1/32768 as capture.py:241-269 does (exact in fp32); ETSI channel filter only. */
+ * scaled by 1/32768 as capture.py:241-269 does (exact in fp32).  Taken by the ETSI channel filter
+ * (the _fmt and stream entry points), the wideband channeliser (tetra_channelize_fmt), the waterfall
+ * and the AFC gate; each entry point's comment names the formats it takes. */
 enum { TETRA_CF32 = 0, TETRA_CF64 = 1, TETRA_SC16 = 2 };
 /* Real samples (float32 / float64), taken only by tetra_demod_dqpsk: the reference's
  * demodulate_dqpsk on a real array (processor.py:124-140 with real scalars). */
@@ -662,6 +664,21 @@ int tetra_channelize(tetra_ctx *ctx, const tetra_wb_plan *plan, const void *x, s
  * ascending; oracle eo_om_group_partials) for tetra_etsi_timing_chunks (and _om).  D = M / 2 plan (up = 36) only. */
 int tetra_channelize_om(tetra_ctx *ctx, const tetra_wb_plan *plan, const void *x, size_t Nw, void *y, size_t n_keep,
                         void *om);
+/* The same two entry points for an explicit capture format: iq_fmt TETRA_CF32 (x [Nw] cf32, what
+ * the two above pass) or TETRA_SC16 (x [Nw][2] int16, I then Q, each scaled by 1/32768: y and om are
+ * those of the cf32 capture x / 32768, bit for bit); any other format is TETRA_E_INVALID.  The
+ * default analysis kernels of both designs load SC16 themselves (4 B per sample read); the two-block
+ * form (TETRA_WB_ANALYSIS=2) and the unfused fold (M != 800) run behind one conversion pass, and the
+ * timing-only TETRA_WB_ANALYSIS_PROBE builds refuse it.  Alignment of x on the device: cf32 as
+ * before, 16 bytes (the fused kernels load two samples per lane; not checked); SC16 8 bytes, two
+ * samples, which is more than int16 pairs have by nature, so a device pointer that is not is refused
+ * with TETRA_E_INVALID before anything is launched (a host array is staged and may sit anywhere).
+ * The D = M / 2 kernels address the capture with 32-bit byte offsets, so it must be under 2 GiB:
+ * 2^28 samples in cf32, 2^29 in SC16. */
+int tetra_channelize_fmt(tetra_ctx *ctx, const tetra_wb_plan *plan, const void *x, int iq_fmt, size_t Nw, void *y,
+                         size_t n_keep);
+int tetra_channelize_om_fmt(tetra_ctx *ctx, const tetra_wb_plan *plan, const void *x, int iq_fmt, size_t Nw, void *y,
+                            size_t n_keep, void *om);
 /* Synthetic wideband capture: M carriers of tetra_synth_etsi bursts at fs/D, filter-bank
  * synthesised to fs, plus AWGN at per-carrier Es/N0 = snr_db.  Outputs as tetra_synth_etsi with
  * C = M and N = Nw / D + 1 (carrier k at +k fs / M, i.e. FFT bin k). */

@@ -35,6 +35,7 @@ enum Slot {
     S_W18,                                                 // compat latency mode: extract_symbols' |y|^2 rows
     S_W19,                                                 // compat, few channels: the mixed rows filtfilt reads
     S_W20,                                                 // compat time-tiled decimator: counters, tile states
+    S_W21,                                                 // wideband: an SC16 capture as cf32 (forms without an SC16 loader)
     S_COUNT
 };
 

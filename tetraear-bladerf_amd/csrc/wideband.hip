@@ -16,7 +16,10 @@
 // v_k differs from the textbook channel output by the constant phase e^{+i 2 pi k / M} (n_j mod M
 // = jD - 1), which the receiver's differential decision and CFO estimate do not see.
 //
-// Bytes: the analysis reads 8 B per wideband sample (the fold's P = 2 re-reads come from L2),
+// The capture comes as cf32 or as TETRA_SC16 (interleaved int16, scaled by 1/32768 where the analysis
+// kernels write it into their LDS ring: tetra_channelize_fmt).
+//
+// Bytes: the analysis reads 8 B per wideband sample, 4 B in SC16 (the fold's P = 2 re-reads come from L2),
 // writes/reads Y once (8 B x M per D input samples = 32 B per input sample at D = 200 -- the FFT
 // stage dominates), and the resampler writes 8 B per 72 kHz output.
 #include <cstdlib>
@@ -63,6 +66,17 @@ __global__ __launch_bounds__(256) void k_pfb_fold(const float2 *__restrict__ x, 
     }
 }
 
+// TETRA_SC16 capture -> cf32 (x / 32768, exact), one sample per thread: in front of the analysis
+// forms without an SC16 loader of their own (k_pfb_analysis2, k_pfb_fold), which then read the same
+// values the native kernels put into their rings.
+__global__ __launch_bounds__(256) void k_pfb_sc16_cf32(const unsigned *__restrict__ x, size_t Nw, float2 *__restrict__ o) {
+    const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= Nw) return;
+    const unsigned w = x[n];
+    const float s = 1.0f / 32768.0f;
+    o[n] = make_float2((float)(short)(w & 0xffffu) * s, (float)((int)w >> 16) * s);
+}
+
 // ---------------------------------------------------------------- fused analysis: fold + FFT
 // Y_j[k] for M = 800 = 8 x 4 x 5 x 5 (mixed-radix Stockham, backward, unnormalised) fused with the
 // fold: a workgroup walks JB consecutive blocks; the wideband samples sit in an LDS ring (each
@@ -83,6 +97,18 @@ __device__ __forceinline__ float2 c_mul(float2 a, float2 b) {
     return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
 }
 __device__ __forceinline__ float2 c_pi(float2 a) { return make_float2(-a.y, a.x); }   // a * (+i)
+
+// A pair of capture samples as the analysis kernels bring it in: cf32 a float4 (re0, im0, re1, im1),
+// TETRA_SC16 a uint2 of four int16 (I0, Q0, I1, Q1).  The ring holds cf32 either way: an SC16 pair
+// is converted where it is written, every component times 2^-15 (exact), so everything behind the
+// ring computes on x / 32768, bit for bit.
+template <bool S16> using an_pair_t = std::conditional_t<S16, uint2, float4>;
+__device__ __forceinline__ float4 an_pair(float4 v) { return v; }
+__device__ __forceinline__ float4 an_pair(uint2 w) {
+    const float s = 1.0f / 32768.0f;
+    return make_float4((float)(short)(w.x & 0xffffu) * s, (float)((int)w.x >> 16) * s,
+                       (float)(short)(w.y & 0xffffu) * s, (float)((int)w.y >> 16) * s);
+}
 
 // backward DFTs (X_k = sum_n a_n e^{+2 pi i n k / R})
 __device__ __forceinline__ void bdft4(float2 &a0, float2 &a1, float2 &a2, float2 &a3) {
@@ -125,10 +151,13 @@ __device__ __forceinline__ void bdft5(float2 *a) {
 // wave's vmcnt counts its loads and stores in one queue: were one wave to do both, waiting for a
 // prefetched load would also wait for every store issued since.  Two frames alternate per block,
 // so a block costs three barriers (after stages 1, 2, 3).
-template <int P>
-__global__ __launch_bounds__(AN_T) void k_pfb_analysis(const float4 *__restrict__ x2, int nblk, int JB,
-                                                       const float *__restrict__ h, const float2 *__restrict__ twg,
-                                                       float2 *__restrict__ Y) {
+// S16: the capture is TETRA_SC16 (k_pfb_analysis_sc16): the loader's registers hold a pair as
+// 8 B, converted as it goes into the ring.
+template <int P, bool S16>
+__device__ __forceinline__ void pfb_analysis_body(const an_pair_t<S16> *__restrict__ x2, int nblk, int JB,
+                                                  const float *__restrict__ h, const float2 *__restrict__ twg,
+                                                  float2 *__restrict__ Y) {
+    using XT = an_pair_t<S16>;
     constexpr int M = AN_M, D = M / 4, L = P * M;
     constexpr int RING = L + D <= 2048 ? 2048 : (L + D <= 4096 ? 4096 : 8192);   // samples, power of 2
     __shared__ float4 ring4[RING / 2];
@@ -142,7 +171,7 @@ __global__ __launch_bounds__(AN_T) void k_pfb_analysis(const float4 *__restrict_
     // the first block's window x[j0 D, j0 D + L) (pairs: j0 D is even)
     for (int q = t; q < L / 2; q += AN_T) {
         const long pr = (long)j0 * (D / 2) + q;
-        ring4[(int)(pr & (RING / 2 - 1))] = x2[pr];
+        ring4[(int)(pr & (RING / 2 - 1))] = an_pair(x2[pr]);
     }
     if (wv == 3) {
         // loader: lane l carries pairs l and l + 64 (< D / 2 = 100) of the new samples of block j,
@@ -154,22 +183,22 @@ __global__ __launch_bounds__(AN_T) void k_pfb_analysis(const float4 *__restrict_
         // four register slots, one per block of the unrolled loop (plain variables and a macro, so
         // they stay in VGPRs), each waited for with the count of the loads issued after it
         static_assert(AN_AF == 8, "loader unroll");
-        float4 s0a = x2[base(j0 + 1) + q0], s0b = x2[base(j0 + 1) + q1];
-        float4 s1a = x2[base(j0 + 2) + q0], s1b = x2[base(j0 + 2) + q1];
-        float4 s2a = x2[base(j0 + 3) + q0], s2b = x2[base(j0 + 3) + q1];
-        float4 s3a = x2[base(j0 + 4) + q0], s3b = x2[base(j0 + 4) + q1];
-        float4 s4a = x2[base(j0 + 5) + q0], s4b = x2[base(j0 + 5) + q1];
-        float4 s5a = x2[base(j0 + 6) + q0], s5b = x2[base(j0 + 6) + q1];
-        float4 s6a = x2[base(j0 + 7) + q0], s6b = x2[base(j0 + 7) + q1];
-        float4 s7a = x2[base(j0 + 8) + q0], s7b = x2[base(j0 + 8) + q1];
+        XT s0a = x2[base(j0 + 1) + q0], s0b = x2[base(j0 + 1) + q1];
+        XT s1a = x2[base(j0 + 2) + q0], s1b = x2[base(j0 + 2) + q1];
+        XT s2a = x2[base(j0 + 3) + q0], s2b = x2[base(j0 + 3) + q1];
+        XT s3a = x2[base(j0 + 4) + q0], s3b = x2[base(j0 + 4) + q1];
+        XT s4a = x2[base(j0 + 5) + q0], s4b = x2[base(j0 + 5) + q1];
+        XT s5a = x2[base(j0 + 6) + q0], s5b = x2[base(j0 + 6) + q1];
+        XT s6a = x2[base(j0 + 7) + q0], s6b = x2[base(j0 + 7) + q1];
+        XT s7a = x2[base(j0 + 8) + q0], s7b = x2[base(j0 + 8) + q1];
         __syncthreads();
 #define AN_LOAD_BLOCK(J, A, B)                                                                  \
         {                                                                                       \
             const int jj = (J);                                                                 \
             if (jj + 1 < j1) {   /* block jj + 1's samples (fetched AF blocks ago) to the ring */ \
                 const long bb = (long)(L + (long)jj * D) / 2;                                   \
-                ring4[(int)((bb + q0) & (RING / 2 - 1))] = A;                                   \
-                if (l + 64 < D / 2) ring4[(int)((bb + l + 64) & (RING / 2 - 1))] = B;           \
+                ring4[(int)((bb + q0) & (RING / 2 - 1))] = an_pair(A);                          \
+                if (l + 64 < D / 2) ring4[(int)((bb + l + 64) & (RING / 2 - 1))] = an_pair(B);  \
             }                                                                                   \
             A = x2[base(jj + 1 + AN_AF) + q0];   /* block jj + 1 + AF's */                      \
             B = x2[base(jj + 1 + AN_AF) + q1];                                                  \
@@ -286,6 +315,19 @@ __global__ __launch_bounds__(AN_T) void k_pfb_analysis(const float4 *__restrict_
         // block j + 1's stage 1 writes the other frame; its stage 2 (after the next barrier) is the
         // first to touch this one again
     }
+}
+
+template <int P>
+__global__ __launch_bounds__(AN_T) void k_pfb_analysis(const float4 *__restrict__ x2, int nblk, int JB,
+                                                       const float *__restrict__ h, const float2 *__restrict__ twg,
+                                                       float2 *__restrict__ Y) {
+    pfb_analysis_body<P, false>(x2, nblk, JB, h, twg, Y);
+}
+template <int P>
+__global__ __launch_bounds__(AN_T) void k_pfb_analysis_sc16(const uint2 *__restrict__ x2, int nblk, int JB,
+                                                            const float *__restrict__ h,
+                                                            const float2 *__restrict__ twg, float2 *__restrict__ Y) {
+    pfb_analysis_body<P, true>(x2, nblk, JB, h, twg, Y);
 }
 
 // Two blocks per iteration (k_pfb_analysis's next step): blocks j and j + 1 go through
@@ -514,10 +556,16 @@ __global__ __launch_bounds__(A2_T, (A2Cfg<P, DM>::WAVES)) void k_pfb_analysis2(c
 // was two thirds of a block's issue time on two of the four SIMDs (profiles/r04_ab_analysis_probe.txt,
 // DESIGN §5.7).  Four barriers per block, fixed frames (X: fold out, stage 2 out; Y: radix-8 out,
 // stage 3 out).  The same fmas in the same order: the same Y.
-template <int P, int DM, bool TREG = true, int PROBE = 0, bool F3 = false>
-__global__ __launch_bounds__(AN_T, (TREG && P <= 5 ? 3 : 2)) void k_pfb_analysis1(const float4 *__restrict__ x2, int nblk, int JB,
-                                                           const float *__restrict__ h,
-                                                           const float2 *__restrict__ twg, float2 *__restrict__ Y) {
+// S16 (k_pfb_analysis1_sc16): the capture is TETRA_SC16.  The loader wave fetches a pair as 8 B (the
+// same lanes, pairs and ring slots; the buffer resource spans the int16 array's bytes) and converts
+// it as it writes the ring; its prefetch slots are half the registers.
+template <int P, int DM, bool TREG, int PROBE, bool F3, bool S16>
+__device__ __forceinline__ void pfb_analysis1_body(const an_pair_t<S16> *__restrict__ x2, int nblk, int JB,
+                                                   const float *__restrict__ h, const float2 *__restrict__ twg,
+                                                   float2 *__restrict__ Y) {
+    using XT = an_pair_t<S16>;
+    constexpr int XB = (int)sizeof(XT);   // bytes per pair of samples
+    static_assert(!S16 || PROBE == 0, "the probe builds are cf32 only");
     using Cf = A2Cfg<P, DM>;
     constexpr int M = Cf::M, D = Cf::D, L = Cf::L, RING = Cf::RING;
     static_assert((P - 1) * M + 768 < RING, "a fold read is at most one ring length behind rbase (rwrap_lo)");
@@ -539,7 +587,7 @@ __global__ __launch_bounds__(AN_T, (TREG && P <= 5 ? 3 : 2)) void k_pfb_analysis
     const long npr = (long)(L + (long)(nblk - 1) * D) / 2;   // pairs of samples any block reads
     const long pr0 = (long)j0 * (D / 2);                      // ring pair 0 = x[j0 D]
     for (int q = t; q < L / 2; q += AN_T)                     // the first block's window
-        if (pr0 + q < npr) ring4[q] = x2[pr0 + q];
+        if (pr0 + q < npr) ring4[q] = an_pair(x2[pr0 + q]);
     // stage 2's radix-4 butterfly b on the fixed F3 frames (Y -> X); with F3 the loader wave's lanes
     // 0-7 take butterflies 192-199, so no compute wave runs two
     auto s2f3 = [&](int b) __attribute__((always_inline)) {
@@ -560,24 +608,29 @@ __global__ __launch_bounds__(AN_T, (TREG && P <= 5 ? 3 : 2)) void k_pfb_analysis
         // block jj (>= 1) adds x[L + (j0 + jj - 1) D, + D): D / 2 pairs from relative pair
         // (L + (jj - 1) D) / 2; written during block jj - 1's stage 1 (disjoint from its window)
         const int l = t - 192;
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(x2), 0, (int)(16 * npr),
+        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<XT *>(x2), 0, (int)(XB * npr),
                                                                             0x00020000);
-        const int vo = 16 * (int)(pr0 + (L - D) / 2 + l);     // block jj's pairs at soffset 8 D jj
+        const int vo = XB * (int)(pr0 + (L - D) / 2 + l);     // block jj's pairs at soffset XB (D / 2) jj
         int rpos = rwrap<RING / 2>(L / 2 + l);                 // ring pair position for block 1
-        float4 sl[AF1][NLD1];
-        auto fetch = [&](float4 (&v)[NLD1], int jj) __attribute__((always_inline)) {
+        XT sl[AF1][NLD1];
+        auto fetch = [&](XT (&v)[NLD1], int jj) __attribute__((always_inline)) {
             if constexpr (PROBE == 1) return;
 #pragma unroll
             for (int m = 0; m < NLD1; ++m) {
-                const nt_f4 w = __builtin_amdgcn_raw_buffer_load_b128(xr, vo + 1024 * m, 8 * D * jj, 0);
-                v[m] = make_float4(w.x, w.y, w.z, w.w);
+                if constexpr (S16) {
+                    const nt_u2 w = __builtin_amdgcn_raw_buffer_load_b64(xr, vo + 64 * XB * m, XB * (D / 2) * jj, 0);
+                    v[m] = make_uint2(w.x, w.y);
+                } else {
+                    const nt_f4 w = __builtin_amdgcn_raw_buffer_load_b128(xr, vo + 64 * XB * m, XB * (D / 2) * jj, 0);
+                    v[m] = make_float4(w.x, w.y, w.z, w.w);
+                }
             }
         };
-        auto step = [&](float4 (&v)[NLD1], int jj) __attribute__((always_inline)) {
+        auto step = [&](XT (&v)[NLD1], int jj) __attribute__((always_inline)) {
             if (jj + 1 < nb) {
 #pragma unroll
                 for (int m = 0; m < NLD1; ++m)
-                    if (l + 64 * m < D / 2) ring4[rwrap<RING / 2>(rpos + 64 * m)] = v[m];
+                    if (l + 64 * m < D / 2) ring4[rwrap<RING / 2>(rpos + 64 * m)] = an_pair(v[m]);
             }
             rpos = rwrap<RING / 2>(rpos + D / 2);
             fetch(v, jj + 1 + AF1);
@@ -738,6 +791,19 @@ __global__ __launch_bounds__(AN_T, (TREG && P <= 5 ? 3 : 2)) void k_pfb_analysis
             }
         }
     }
+}
+
+template <int P, int DM, bool TREG = true, int PROBE = 0, bool F3 = false>
+__global__ __launch_bounds__(AN_T, (TREG && P <= 5 ? 3 : 2)) void k_pfb_analysis1(const float4 *__restrict__ x2, int nblk, int JB,
+                                                           const float *__restrict__ h,
+                                                           const float2 *__restrict__ twg, float2 *__restrict__ Y) {
+    pfb_analysis1_body<P, DM, TREG, PROBE, F3, false>(x2, nblk, JB, h, twg, Y);
+}
+template <int P, int DM, bool TREG = true, bool F3 = false>
+__global__ __launch_bounds__(AN_T, (TREG && P <= 5 ? 3 : 2)) void k_pfb_analysis1_sc16(const uint2 *__restrict__ x2, int nblk,
+                                                           int JB, const float *__restrict__ h,
+                                                           const float2 *__restrict__ twg, float2 *__restrict__ Y) {
+    pfb_analysis1_body<P, DM, TREG, 0, F3, true>(x2, nblk, JB, h, twg, Y);
 }
 
 // y[k][n] for 64 channels x RS_T outputs: v rows staged (rotated) in LDS, one lane per channel,
@@ -992,10 +1058,17 @@ int tetra_wb_lengths(const tetra_wb_plan *P, size_t Nw, int64_t *nblk, int64_t *
 }
 
 namespace {
-int channelize(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, size_t Nw, void *y, size_t n_keep, void *om) {
+int channelize(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, int iq_fmt, size_t Nw, void *y, size_t n_keep,
+               void *om) {
     if (!ctx) return TETRA_E_INVALID;
     int rc = wb_check(ctx, P);
     if (rc) return rc;
+    if (iq_fmt != TETRA_CF32 && iq_fmt != TETRA_SC16)
+        return tetra_fail(ctx, TETRA_E_INVALID, "wideband capture format %d: TETRA_CF32 or TETRA_SC16", iq_fmt);
+    const bool s16 = iq_fmt == TETRA_SC16;
+    // the SC16 loaders fetch a pair of samples (8 B) per lane; a host capture is staged aligned
+    if (s16 && x && ((uintptr_t)x & 7) && is_device_ptr(x))
+        return tetra_fail(ctx, TETRA_E_INVALID, "SC16 capture on the device must be 8-byte aligned");
     int64_t nblk, n72;
     tetra_wb_lengths(P, Nw, &nblk, &n72);
     if (n72 <= 0 || n_keep == 0 || (int64_t)n_keep > n72)
@@ -1011,7 +1084,7 @@ int channelize(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, size_t Nw,
         return tetra_fail(ctx, TETRA_E_INVALID, "Oerder-Meyr group partials need the D = M / 2 resampler (36 / 25)");
     const int ngrp = (int)((n_keep + P->up - 1) / P->up);
     Staging st(ctx);
-    const float2 *xd = (const float2 *)st.in(x, Nw * 8);
+    const void *xd = st.in(x, Nw * (s16 ? 4 : 8));
     float2 *yd = (float2 *)st.out(y, (size_t)M * n_keep * 8);
     float4 *omd = om ? (float4 *)st.out(om, (size_t)M * ngrp * 16) : nullptr;
     float2 *u = (float2 *)ws(ctx, S_W8, (size_t)nblk * M * 8);
@@ -1045,6 +1118,28 @@ int channelize(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, size_t Nw,
     // fold + FFT in one pass (k_pfb_analysis / k_pfb_analysis2); D = M / 2 only so
     const bool fused = M == AN_M && ((DM == 1 && P->P <= 4) || (DM == 2 && P->P >= 4 && P->P <= 6));
     if (!fused && DM != 1) return tetra_fail(ctx, TETRA_E_INVALID, "D = M / 2 needs M = 800 and 4 <= P <= 6");
+    // TETRA_WB_ANALYSIS (below) picks the fused kernel.  SC16: the one-block kernels of both designs
+    // load it themselves; in front of the two-block form and the unfused fold it is converted once
+    // into a workspace (x / 32768, the values the native loaders write into their rings).
+    const char *fe = getenv("TETRA_WB_ANALYSIS");
+    const int form = fe ? atoi(fe) : 1;
+    const char *pe = getenv("TETRA_WB_ANALYSIS_PROBE");
+    const int probe = pe ? atoi(pe) : 0;
+    const bool one_dm2 = fused && DM == 2 && form != 2;
+    const bool one_dm1 = fused && DM == 1 && (form != 2 || Nw * 8 >= (size_t)1 << 31);
+    if (s16 && one_dm2 && probe != 0)
+        return tetra_fail(ctx, TETRA_E_INVALID, "TETRA_WB_ANALYSIS_PROBE builds take cf32 only");
+    const bool native16 = s16 && (one_dm2 || one_dm1);
+    if (s16 && !native16) {
+        PROF(ctx, "wb_sc16");
+        float2 *xc = (float2 *)ws(ctx, S_W21, Nw * 8);
+        if (!xc) return st.finish();
+        hipLaunchKernelGGL(k_pfb_sc16_cf32, dim3(grid_for(Nw, 256)), dim3(256), 0, ctx->stream, (const unsigned *)xd, Nw,
+                           xc);
+        HIP_TRY(ctx, hipGetLastError());
+        xd = xc;
+    }
+    const size_t xbytes = Nw * (native16 ? 4 : 8);   // of the array the analysis reads
     const size_t tw_off = ctx->taps_wb.size() + (ctx->taps_wb.size() & 1);   // float2-aligned
     if (fused) {   // backward twiddles e^{+2 pi i m r / (Ns R)}, r-major per stage
         ctx->taps_wb.resize(tw_off + 2 * AN_TWN, 0.f);
@@ -1073,24 +1168,32 @@ int channelize(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, size_t Nw,
         // iteration (default), 2 two blocks per iteration (k_pfb_analysis2), 3 / 4 (D = M / 2) one
         // block with every twiddle in LDS / with the fold inside the radix-8 butterflies -- same-box
         // A/B and the parity tests, which switch it between calls.  The D = M / 2 kernels address the capture
-        // with 32-bit byte offsets.
-        const char *fe = getenv("TETRA_WB_ANALYSIS");
-        const int form = fe ? atoi(fe) : 1;
-        if (DM == 2 && Nw * 8 >= (size_t)1 << 31)
+        // with 32-bit byte offsets: 2 GiB of it, twice the samples in SC16 as in cf32.
+        if (DM == 2 && xbytes >= (size_t)1 << 31)
             return tetra_fail(ctx, TETRA_E_INVALID, "D = M / 2 capture over 2 GiB: split it");
-        if (DM == 2 && form != 2) {
+        if (one_dm2) {
             // three (P <= 5, twiddles in registers) or two 256-thread workgroups per CU, >= 16 blocks
             // each, about one round
             const bool treg = form != 3;
             const int per_cu = treg && P->P <= 5 ? 3 : 2;
             const int jb = std::max<int>(16, (int)((nblk + per_cu * 256 - 1) / (per_cu * 256)));
             const unsigned grid = (unsigned)((nblk + jb - 1) / jb);
-            const char *pe = getenv("TETRA_WB_ANALYSIS_PROBE");
-            const int probe = pe ? atoi(pe) : 0;
             // the default: twiddles in registers and the fold on three waves (F3); 4: without F3, 3:
             // without either (same-box A/B, profiles/r04_ab_analysis_f3_*.txt)
             const bool f3 = form != 3 && form != 4;
-            if (f3 && probe == 0) {
+            if (native16 && f3) {
+                switch (P->P) {
+#define AN(PP) case PP: hipLaunchKernelGGL((k_pfb_analysis1_sc16<PP, 2, true, true>), dim3(grid), dim3(AN_T), 0, ctx->stream, (const uint2 *)xd, (int)nblk, jb, taps, (const float2 *)(taps + tw_off), u); break;
+                    AN(4) AN(5) AN(6)
+#undef AN
+                }
+            } else if (native16) {
+                switch (P->P * 2 + (treg ? 1 : 0)) {
+#define AN(PP, TR) case PP * 2 + TR: hipLaunchKernelGGL((k_pfb_analysis1_sc16<PP, 2, TR>), dim3(grid), dim3(AN_T), 0, ctx->stream, (const uint2 *)xd, (int)nblk, jb, taps, (const float2 *)(taps + tw_off), u); break;
+                    AN(4, 0) AN(5, 0) AN(6, 0) AN(4, 1) AN(5, 1) AN(6, 1)
+#undef AN
+                }
+            } else if (f3 && probe == 0) {
                 switch (P->P) {
 #define AN(PP) case PP: hipLaunchKernelGGL((k_pfb_analysis1<PP, 2, true, 0, true>), dim3(grid), dim3(AN_T), 0, ctx->stream, (const float4 *)xd, (int)nblk, jb, taps, (const float2 *)(taps + tw_off), u); break;
                     AN(4) AN(5) AN(6)
@@ -1108,9 +1211,16 @@ int channelize(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, size_t Nw,
                 AN(4, 0) AN(5, 0) AN(6, 0) AN(4, 1) AN(5, 1) AN(6, 1)
 #undef AN
             }
-        } else if (DM == 1 && (form != 2 || Nw * 8 >= (size_t)1 << 31)) {
+        } else if (one_dm1) {
             const int jb = std::max<int>(16, (int)((nblk + 4 * 256 - 1) / (4 * 256)));
             const unsigned grid = (unsigned)((nblk + jb - 1) / jb);
+            if (native16)
+            switch (P->P) {
+#define AN(PP) case PP: hipLaunchKernelGGL(k_pfb_analysis_sc16<PP>, dim3(grid), dim3(AN_T), 0, ctx->stream, (const uint2 *)xd, (int)nblk, jb, taps, (const float2 *)(taps + tw_off), u); break;
+                AN(1) AN(2) AN(3) AN(4)
+#undef AN
+            }
+            else
             switch (P->P) {
 #define AN(PP) case PP: hipLaunchKernelGGL(k_pfb_analysis<PP>, dim3(grid), dim3(AN_T), 0, ctx->stream, (const float4 *)xd, (int)nblk, jb, taps, (const float2 *)(taps + tw_off), u); break;
                 AN(1) AN(2) AN(3) AN(4)
@@ -1136,7 +1246,7 @@ int channelize(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, size_t Nw,
         constexpr int JB = 16;
         const dim3 gr((unsigned)((M + 255) / 256), (unsigned)((nblk + JB - 1) / JB));
         switch (P->P) {
-#define FOLD(PP) case PP: hipLaunchKernelGGL(k_pfb_fold<PP>, gr, dim3(256), 0, ctx->stream, xd, M, P->D, (int)nblk, taps, u, JB); break;
+#define FOLD(PP) case PP: hipLaunchKernelGGL(k_pfb_fold<PP>, gr, dim3(256), 0, ctx->stream, (const float2 *)xd, M, P->D, (int)nblk, taps, u, JB); break;
             FOLD(1) FOLD(2) FOLD(3) FOLD(4) FOLD(5) FOLD(6) FOLD(7) FOLD(8)
 #undef FOLD
         }
@@ -1193,14 +1303,24 @@ int channelize(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, size_t Nw,
 }
 }  // namespace
 
+int tetra_channelize_fmt(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, int iq_fmt, size_t Nw, void *y,
+                         size_t n_keep) {
+    return channelize(ctx, P, x, iq_fmt, Nw, y, n_keep, nullptr);
+}
+
+int tetra_channelize_om_fmt(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, int iq_fmt, size_t Nw, void *y,
+                            size_t n_keep, void *om) {
+    if (!om) return tetra_fail(ctx, TETRA_E_INVALID, "null om");
+    return channelize(ctx, P, x, iq_fmt, Nw, y, n_keep, om);
+}
+
 int tetra_channelize(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, size_t Nw, void *y, size_t n_keep) {
-    return channelize(ctx, P, x, Nw, y, n_keep, nullptr);
+    return tetra_channelize_fmt(ctx, P, x, TETRA_CF32, Nw, y, n_keep);
 }
 
 int tetra_channelize_om(tetra_ctx *ctx, const tetra_wb_plan *P, const void *x, size_t Nw, void *y, size_t n_keep,
                         void *om) {
-    if (!om) return tetra_fail(ctx, TETRA_E_INVALID, "null om");
-    return channelize(ctx, P, x, Nw, y, n_keep, om);
+    return tetra_channelize_om_fmt(ctx, P, x, TETRA_CF32, Nw, y, n_keep, om);
 }
 
 int tetra_synth_wideband(tetra_ctx *ctx, const tetra_wb_plan *P, size_t Nw, uint64_t seed, float snr_db,

@@ -162,6 +162,8 @@ def _bind(L):
         "tetra_scan_detect": (_i32, [_vp, _vp, _i32, _sz, _sz, _i32, ctypes.c_uint32, _vp]),
         "tetra_channelize": (_i32, [_vp, ctypes.POINTER(WbPlan), _vp, _sz, _vp, _sz]),
         "tetra_channelize_om": (_i32, [_vp, ctypes.POINTER(WbPlan), _vp, _sz, _vp, _sz, _vp]),
+        "tetra_channelize_fmt": (_i32, [_vp, ctypes.POINTER(WbPlan), _vp, _i32, _sz, _vp, _sz]),
+        "tetra_channelize_om_fmt": (_i32, [_vp, ctypes.POINTER(WbPlan), _vp, _i32, _sz, _vp, _sz, _vp]),
         "tetra_synth_wideband": (_i32, [_vp, ctypes.POINTER(WbPlan), _sz, ctypes.c_uint64, ctypes.c_float,
                                         ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
         "tetra_synth_bursts_per_channel": (_i32, [_sz, ctypes.c_double]),

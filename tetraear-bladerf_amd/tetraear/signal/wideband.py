@@ -7,7 +7,8 @@ spacing and splits it on the device: a polyphase filter bank (libtetra_hip.so k_
 + 800-point FFT fused, two blocks per iteration; D = M / 2 by default, so every carrier comes out at
 50 kHz), then per carrier an RRC(0.35) matched-filter resampler to 72 kHz (k_pfb_resamp_fix), which
 is exactly the sample stream the ETSI timing stage takes (4 samples per symbol, tetra_etsi_timing),
-followed by the ETSI lower MAC.  This module designs the filters and moves arrays;
+followed by the ETSI lower MAC.  The capture goes in as complex64 or as the radio's SC16 ([Nw, 2]
+int16, scaled 1/32768 in the analysis kernel's loader).  This module designs the filters and moves arrays;
 oracle/wideband.py is the float64 specification the tests hold it to.
 """
 import collections
@@ -142,8 +143,27 @@ def grouped_om(plan, m2=M2_CHUNK):
             and os.environ.get("TETRA_WB_OM", "1") != "0")
 
 
+def sc16_to_cf32(x):
+    """[Nw, 2] int16 -> [Nw] complex64 scaled 1/32768 (exact): the capture the SC16 kernels compute on."""
+    return ((x[..., 0].astype(np.float32) + 1j * x[..., 1].astype(np.float32)) / np.float32(32768)).astype(
+        np.complex64)
+
+
+def _capture(x):
+    """A capture as the library takes it: int16 input is SC16, [Nw, 2] (I, Q) as the radio delivers
+    it, and goes in as it is; anything else becomes [Nw] complex64.  Returns (array, iq_fmt)."""
+    x = np.asarray(x)
+    if x.dtype == np.int16:
+        if x.ndim != 2 or x.shape[-1] != 2:
+            raise ValueError("SC16 input must be [Nw, 2] int16")
+        return np.ascontiguousarray(x), _hip.TETRA_SC16
+    return np.ascontiguousarray(x, np.complex64), _hip.TETRA_CF32
+
+
 class WidebandReceiver:
-    """Channeliser + per-carrier ETSI demod (timing, decision) for host or device arrays."""
+    """Channeliser + per-carrier ETSI demod (timing, decision) for host or device arrays.  Every
+    method that takes a capture x takes it as [Nw] complex or as [Nw, 2] int16 (SC16, scaled 1/32768 on
+    the device): the results are those of the complex64 capture x / 32768, bit for bit."""
 
     def __init__(self, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None):
         self.plan = wb_plan(fs, M, oversample)
@@ -151,30 +171,31 @@ class WidebandReceiver:
         self.m2 = m2
 
     def channelize(self, x, n_keep=None):
-        """x [Nw] complex64 -> y [M][n_keep] complex64 at 72 kHz."""
+        """x [Nw] complex64 or [Nw, 2] int16 -> y [M][n_keep] complex64 at 72 kHz."""
+        x, fmt = _capture(x)
         c = _hip.ctx()
-        x = np.ascontiguousarray(x, np.complex64)
         _, n72 = self.plan.lengths(len(x))
         n_keep = n72 if n_keep is None else n_keep
         y = np.empty((self.plan.M, n_keep), np.complex64)
         if n_keep == 0:   # a capture shorter than one 72 kHz output (the oracle's [M, 0])
             return y
-        c.check(c.lib.tetra_channelize(c.handle, self.plan.c, _hip.ptr(x), len(x), _hip.ptr(y), n_keep), "channelize")
+        c.check(c.lib.tetra_channelize_fmt(c.handle, self.plan.c, _hip.ptr(x), fmt, len(x), _hip.ptr(y), n_keep),
+                "channelize")
         return y
 
     def channelize_om(self, x, n_keep=None):
         """channelize plus the resampler's Oerder-Meyr group partials: (y [M][n_keep] complex64,
         om [M][ceil(n_keep / up)][4] float32) -- D = M / 2 plan only (tetra_channelize_om)."""
+        x, fmt = _capture(x)
         c = _hip.ctx()
-        x = np.ascontiguousarray(x, np.complex64)
         _, n72 = self.plan.lengths(len(x))
         n_keep = n72 if n_keep is None else n_keep
         y = np.empty((self.plan.M, n_keep), np.complex64)
         om = np.empty((self.plan.M, -(-n_keep // self.plan.c.up), 4), np.float32)
         if n_keep == 0:
             return y, om
-        c.check(c.lib.tetra_channelize_om(c.handle, self.plan.c, _hip.ptr(x), len(x), _hip.ptr(y), n_keep,
-                                          _hip.ptr(om)), "channelize_om")
+        c.check(c.lib.tetra_channelize_om_fmt(c.handle, self.plan.c, _hip.ptr(x), fmt, len(x), _hip.ptr(y), n_keep,
+                                              _hip.ptr(om)), "channelize_om")
         return y, om
 
     def grouped_om(self):
@@ -185,6 +206,7 @@ class WidebandReceiver:
     def demod(self, x):
         """x [Nw] -> (hard, soft_bits, sym, nsym) per (carrier, chunk) of chunking(): [M, nchunk,
         smax] uint8, [M, nchunk, 2 smax] int8, [M, nchunk, smax] complex64, [M, nchunk] int32."""
+        x, _ = _capture(x)
         ck = chunking(self.plan, len(x), self.m2)
         om = None
         if self.grouped_om():
@@ -318,7 +340,12 @@ class WidebandStream:
     ``mac=True``: the blocks carry ``npdu`` / ``pdus`` (WidebandReceiver.decode).  ``timebase=True``
     (implies it): the frames carry ``tn`` / ``fn`` / ``mn`` / ``slot_flags`` from one TDMA timebase per
     carrier, carried from piece to piece in ``tdma`` [M] (reset() clears it): a buffer's carried tail
-    is decoded again behind the anchor, which places those bursts without moving it."""
+    is decoded again behind the anchor, which places those bursts without moving it.
+
+    The pieces may be [n, 2] int16 (SC16, a recording or the radio's buffer as it is): the tail is
+    then kept in int16 and the buffer goes to the device in 4 B per sample.  If the pieces change
+    format, whichever of tail and piece is int16 is converted (x / 32768, exact) and the buffer is
+    complex64, so a mixed stream gives what the complex64 stream does."""
     CARRY_Y = 2 * BURST_SAMPLES
 
     def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False, timebase=False):
@@ -370,7 +397,11 @@ class WidebandStream:
     def decode(self, x):
         """x: the next samples of the capture -> per carrier the frames first decoded now, each with
         "stream_sample" (its start in the carrier's 72 kHz stream)."""
-        buf = np.concatenate([self.tail, np.asarray(x, np.complex64)])
+        x, _ = _capture(x)
+        tail = self.tail
+        if len(tail) and tail.dtype != x.dtype:   # the format changed: go on in complex64
+            tail, x = (sc16_to_cf32(a) if a.dtype == np.int16 else a for a in (tail, x))
+        buf = np.concatenate([tail, x]) if len(tail) else x
         _, n72 = self.rx.plan.lengths(len(buf))
         out = [[] for _ in range(self.M)]
         T = max(0, (n72 - self.CARRY_Y) // self.ups) * self.per   # the next buffer starts here
@@ -386,7 +417,7 @@ class WidebandStream:
                         f["stream_sample"] = int(a)
                         out[k].append(f)
                         self.last[k] = a
-        self.tail = buf[T:]
+        self.tail = buf[T:].copy()   # (the buffer may be the caller's array)
         self.y0 += dy
         return out
 
@@ -432,12 +463,33 @@ class BenchStep:
     device from step to step with the context that runs the lower MAC.  TETRA_WB_MAC=timebase: the
     capture is synthesised on the slot grid and tetra_etsi_mac_groups follows the lower MAC on the same
     context (PDU headers, the merge of each carrier's chunk rows, one TDMA timebase per carrier resident
-    on the device; every step decodes the same capture, so bit0 does not advance)."""
+    on the device; every step decodes the same capture, so bit0 does not advance).  TETRA_WB_IQ=sc16
+    (default cf32): the capture is resident as the radio's int16 pairs -- the synthesised sum of 800
+    carriers scaled by the smallest power of two that brings it into full scale, rounded -- and the
+    channeliser and the waterfall take it as TETRA_SC16."""
     dtype = "f32 (DSP), int8/int32 (Viterbi)"
+
+    @staticmethod
+    def iq_format():
+        """TETRA_WB_IQ: "cf32" (default) or "sc16"."""
+        iq = os.environ.get("TETRA_WB_IQ", "cf32")
+        if iq not in ("cf32", "sc16"):
+            raise ValueError(f"TETRA_WB_IQ={iq!r}: cf32 or sc16")
+        return iq
+
+    @staticmethod
+    def sc16_shift(peak):
+        """The smallest k >= 0 with peak * 2^-k * 32768 <= 32767 (peak = max(|re|, |im|) of the capture)."""
+        k = 0
+        while peak * 2.0 ** -k * 32768.0 > 32767.0:
+            k += 1
+        return k
 
     def __init__(self, c, Nw, seed, device, snr_db=30.0, fs=FS_WB, M=M_WB):
         import torch
         self.c, self.Nw, self.fs = c, Nw, fs
+        self.iq_name = self.iq_format()
+        self.fmt = _hip.TETRA_SC16 if self.iq_name == "sc16" else _hip.TETRA_CF32
         self.plan = wb_plan(fs, M)
         self.etsi = etsi_plan(2.4e6)
         self.ck = chunking(self.plan, Nw)
@@ -462,6 +514,9 @@ class BenchStep:
         if self.timebase:
             c.check(c.lib.tetra_synth_set_grid(c.handle, 0), "synth_set_grid")
         c.synchronize()   # torch's ops below need not share the context's stream
+        if self.iq_name == "sc16":   # only the int16 capture is kept
+            self.sc16_k = self.sc16_shift(float(self.x.abs().max()))
+            self.x = torch.round(self.x * (32768.0 * 2.0 ** -self.sc16_k)).clamp_(-32768, 32767).to(torch.int16)
         # every chunk of carrier k uses carrier k's scrambling code
         self.cells = cells.repeat_interleave(self.nchunk).contiguous()
         mode = os.environ.get("TETRA_WB_CELLS", "given")
@@ -562,18 +617,18 @@ class BenchStep:
         return [self.c] + ([self.back] if self.pipelined else []) + ([self.mid] if self.mid is not None else [])
 
     def _waterfall(self, c):
-        c.check(c.lib.tetra_waterfall(c.handle, _hip.ptr(self.x), _hip.TETRA_CF32, 1, self.Nw, 2048, 2048, self.nfr,
+        c.check(c.lib.tetra_waterfall(c.handle, _hip.ptr(self.x), self.fmt, 1, self.Nw, 2048, 2048, self.nfr,
                                       _hip.ptr(self.wf)), "waterfall")
 
     def _front(self, c, y, om):
         if not (self.pipelined and self.wf_back):
             self._waterfall(c)
         if om is not None:
-            c.check(c.lib.tetra_channelize_om(c.handle, self.plan.c, _hip.ptr(self.x), self.Nw, _hip.ptr(y),
-                                              self.ck.rowlen, _hip.ptr(om)), "channelize_om")
+            c.check(c.lib.tetra_channelize_om_fmt(c.handle, self.plan.c, _hip.ptr(self.x), self.fmt, self.Nw,
+                                                  _hip.ptr(y), self.ck.rowlen, _hip.ptr(om)), "channelize_om")
         else:
-            c.check(c.lib.tetra_channelize(c.handle, self.plan.c, _hip.ptr(self.x), self.Nw, _hip.ptr(y),
-                                           self.ck.rowlen), "channelize")
+            c.check(c.lib.tetra_channelize_fmt(c.handle, self.plan.c, _hip.ptr(self.x), self.fmt, self.Nw,
+                                               _hip.ptr(y), self.ck.rowlen), "channelize")
 
     def _timing(self, c, y, om):
         ck = self.ck
@@ -644,7 +699,7 @@ class BenchStep:
         self.ev_back[i].record(self.s_back)
 
     def stage_bytes(self):
-        """Algorithmic bytes per wideband input sample of each timed stage (cf32 = 8 B):
+        """Algorithmic bytes per wideband input sample of each timed stage (cf32 = 8 B, SC16 = 4 B in):
         the fused analysis (M = 800) and the fold read x and write Y (M per D samples), the FFT reads and writes Y, the resampler reads
         Y and writes y (M carriers at 72 kHz), the timing stage reads y and writes per symbol an
         8 B symbol, 2 soft bits and a hard dibit -- the samples two chunks share twice (cover =
@@ -652,17 +707,19 @@ class BenchStep:
         M, D, fs, ck = self.plan.M, self.plan.D, self.fs, self.ck
         yb = 8.0 * M * 72000.0 / fs
         cover = ((ck.nchunk - 1) * ck.length + ck.rowlen - (ck.nchunk - 1) * ck.stride) / ck.rowlen
+        xb = 4.0 if self.iq_name == "sc16" else 8.0   # input bytes per sample
+        # (SC16 in front of the two-block form: its conversion pass is the stage "wb_sc16", not counted)
         ana = "k_pfb_analysis2" if os.environ.get("TETRA_WB_ANALYSIS") == "2" else \
-            ("k_pfb_analysis1" if self.plan.oversample == 2 else "k_pfb_analysis")
-        return {"waterfall": (12.0 * self.nfr * 2048 / self.Nw, "k_waterfall"),
-                "wb_analysis": (8.0 + 8.0 * M / D, ana),   # fused fold + FFT: x in, Y out
-                "wb_fold": (8.0 + 8.0 * M / D, "k_pfb_fold"), "wb_fft": (2 * 8.0 * M / D, None),
+            (("k_pfb_analysis1" if self.plan.oversample == 2 else "k_pfb_analysis") + ("_sc16" if self.iq_name == "sc16" else ""))
+        return {"waterfall": ((xb + 4.0) * self.nfr * 2048 / self.Nw, "k_waterfall"),
+                "wb_analysis": (xb + 8.0 * M / D, ana),   # fused fold + FFT: x in, Y out
+                "wb_fold": (xb + 8.0 * M / D, "k_pfb_fold"), "wb_fft": (2 * 8.0 * M / D, None),
                 "wb_resamp": (8.0 * M / D + yb + (yb * 2.0 / self.plan.c.up if self.om_grouped else 0.0),
                               "k_pfb_resamp_fix"),
                 "etsi_timing": (cover * (yb + 11.0 * M * 18000.0 / fs), "k_timing")}
 
     def config(self, world):
-        return {"workload": f"C3: {self.Nw} samples of a {self.fs / 1e6:g} MSps capture per GPU, "
+        return {"workload": f"C3: {self.Nw} {'SC16 ' if self.iq_name == 'sc16' else ''}samples of a {self.fs / 1e6:g} MSps capture per GPU, "
                             f"{self.plan.M} carriers x {self.nchunk} timing chunks of {self.ck.length} "
                             f"every {self.m2}",
                 "wideband_samples_per_gpu": self.Nw, "sample_rate": self.fs, "carriers": self.plan.M,
@@ -672,13 +729,17 @@ class BenchStep:
                 "pipeline": self.pipelined,
                 # (bench.py adds cells_mode itself only to the config it builds for steps without one)
                 **({"cells": self.cells_mode} if self.acquire else {}),
-                **({"mac": "timebase"} if self.timebase else {})}
+                **({"mac": "timebase"} if self.timebase else {}),
+                **({"iq": "sc16", "sc16_scale": f"2^-{self.sc16_k}"} if self.iq_name == "sc16" else {})}
 
     def realtime_channels(self, value_msps):
         return value_msps * 1e6 / self.fs * self.plan.M   # carriers served at real time
 
     def workload_key(self):
-        return f"C3: {self.Nw} samples"   # a substring of config()["workload"]
+        # a substring of config()["workload"]; an SC16 step's says so ("... SC16 samples"), and neither
+        # key is a substring of the other's workload, so a profile summary of one format is never read
+        # for the other
+        return f"C3: {self.Nw} samples" if self.iq_name == "cf32" else f"C3: {self.Nw} SC16 samples"
 
     def quality(self):
         """The last step's decoded work, each burst once (merge_chunks): bursts, blocks, CRC-good

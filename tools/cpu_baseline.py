@@ -128,7 +128,10 @@ def wideband_rate(step, seconds):
     d = W.design(step.fs, step.plan.M)
     L, m2 = step.ck.length, step.m2
     nw = (L * DOWN) // UP * step.plan.D + step.plan.M * P_WB + 64 * step.plan.D   # one chunk per carrier
-    x = step.x[:nw].cpu().numpy().view(np.complex64)[:, 0]
+    x = step.x[:nw].cpu().numpy()
+    if x.dtype == np.int16:   # TETRA_WB_IQ=sc16: the samples the device computes on
+        x = (x.astype(np.float32) / np.float32(32768))
+    x = np.ascontiguousarray(x).view(np.complex64)[:, 0]
     t0 = time.perf_counter()
     y = W.channelize(x.astype(np.complex128), d, L).astype(np.complex64)
     t_ch = time.perf_counter() - t0
