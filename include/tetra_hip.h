@@ -606,6 +606,49 @@ int tetra_etsi_mac_groups(tetra_ctx *ctx, const int32_t *nsym, size_t C, size_t 
                           int32_t *slots /*[C][MAXB][4]*/, int32_t *npdu /*[C][MAXJ]*/,
                           int32_t *pdus /*[C][MAXJ][MAXPDU][16]*/);
 
+/* Link quality of the ETSI chain's bursts and blocks (a new symbol of ABI version 2; nothing existing
+ * changed shape): how many channel bits the decoder corrected in a block, how many known bits of a
+ * burst were wrong, how strong the soft bits were.  It stands in for the signal-quality read-out of
+ * the reference's capture loop; on decoded blocks the reference has no counterpart.  All exact
+ * integers, restated in tests/_etsi_quality_model.py.
+ *
+ * Inputs: the rows softbits [C][2 stride] / hard [C][stride] a lower-MAC call read, still intact, and
+ * that call's outputs.  origin_bits: the row bit the start bits count from -- 0 for tetra_lmac_etsi,
+ * _acquire and _acquire_groups, 2 * TETRA_ETSI_RESERVE for tetra_lmac_etsi_stream (whose start bits may
+ * be negative; stream into next rows other than the input rows, or the rows read are gone).
+ * cell_init [C / G]: the scrambling init rows g G .. g G + G - 1 were descrambled with (the
+ * configured init, or the value the acquire call returned); the sequences are formed on the device
+ * from it, whatever the context's cell table holds.
+ *
+ * bq [C][MAXB][TETRA_LQ_FIELDS], for b < nburst[c] (clamped to 0..MAXB; nothing past it written).  A
+ * burst is invalid when its kind is outside 0..2 or row bits origin_bits + start .. + 510 do not lie
+ * inside the row's 2 stride bits: nothing of it is read and it reads -1, -1, -1, -1.  Else, a hard
+ * bit at row bit p being hard[c][p >> 1] bit (p & 1 ? 0 : 1) and every position relative to
+ * origin_bits + start: TERR the training bits that differ from the kind's sequence (22 at 244 for
+ * n / p, 38 at 214 for y), HERR the differing bits among the 12 head bits at 0 and the 10 tail bits
+ * at 500, WSUM the sum of |soft| over the 510 bits (|-128| = 128), NSAT those with |soft| >= 127.
+ *
+ * kq [C][MAXJ][TETRA_LQ_FIELDS], for j < nblock[c] (clamped likewise).  Block j of kind k (K = 432 /
+ * 216 / 120 coded bits) lies at offset 282 of its burst for block index 1, else 14 (SCH/F, SCH/HD)
+ * or 94 (BSCH); SCH/F's coded bits from 216 on lie 52 bits further.  A CRC-bad block reads -1, 0, 0,
+ * 0.  A block of an invalid burst -- or one that names no live burst, a kind outside 0..2, or a
+ * block index its kind does not have -- reads -1, -1, -1, -1.  Else its type-1 bits (byte & 1) are
+ * encoded as by tetra_etsi_encode_blocks (BSCH with scrambler init 3, else the row's cell) into
+ * c_0 .. c_K-1 and compared with the soft values s_i at those row bits: NERR the positions with
+ * s_i != 0 and (s_i < 0) != (c_i == 1), WERR the sum of |s_i| over them, WSUM the sum of |s_i| over
+ * all K, NZERO the positions with s_i == 0.
+ *
+ * C == 0, stride == 0, G == 0, C % G != 0, origin_bits < 0 or a NULL array: TETRA_E_INVALID, nothing
+ * written.  Host or device pointers; with device pointers the call enqueues one kernel on the context
+ * stream and returns without waiting (no allocation, no synchronising copy). */
+enum { TETRA_LQ_NERR = 0, TETRA_LQ_WERR, TETRA_LQ_WSUM, TETRA_LQ_NZERO, TETRA_LQ_FIELDS = 4 };
+enum { TETRA_BQ_TERR = 0, TETRA_BQ_HERR, TETRA_BQ_WSUM, TETRA_BQ_NSAT };
+int tetra_etsi_link_quality(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, size_t C, size_t stride,
+                            int32_t origin_bits, size_t G, const uint32_t *cell_init /*[C/G]*/,
+                            const int32_t *nburst, const int32_t *bursts, const int32_t *nblock,
+                            const int32_t *blocks, const uint8_t *type1,
+                            int32_t *bq /*[C][MAXB][4]*/, int32_t *kq /*[C][MAXJ][4]*/);
+
 /* The ETSI receiver's AFC mixer on a streaming window: out [C][N] cf32 = iq (cf32 rows ld samples
  * apart) x exp(-j 2 pi f (n0 + n) / fs), n0 = the window's first sample in the capture (frequency_shift's
  * float64 arithmetic, processor.py:85-100, with one continuous phase across windows); mix_c [C] as

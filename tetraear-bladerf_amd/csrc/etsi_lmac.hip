@@ -19,32 +19,11 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "etsi_coding.h"   // block kinds, burst patterns, puncturer, CRC and scrambler tables
 
 namespace {
 
-constexpr int ETSI_MAXB = 8;   // bursts per channel chunk
-constexpr int ETSI_MAXJ = 16;   // coded blocks per channel chunk (2 per burst)
-
-struct KindP { int K, a, n2, n1; };
-__host__ __device__ constexpr KindP kind_params(int kind) {
-    return kind == 0 ? KindP{432, 103, 288, 268} : kind == 1 ? KindP{216, 101, 144, 124} : KindP{120, 11, 80, 60};
-}
-
 // --------------------------------------------------------------------------- E3/E4 lower MAC
-// training/tail patterns (EN 300 392-2 §9.4.4.3), LSB-first words
-__host__ __device__ constexpr uint64_t packb(const int *p, int n) {
-    uint64_t w = 0;
-    for (int j = 0; j < n; ++j) w |= (uint64_t)p[j] << j;
-    return w;
-}
-constexpr int QB[22] = {1, 0, 1, 1, 0, 1, 1, 1, 0, 0, 0, 0, 0, 1, 1, 0, 1, 0, 1, 1, 0, 1};
-constexpr int NB[22] = {1, 1, 0, 1, 0, 0, 0, 0, 1, 1, 1, 0, 1, 0, 0, 1, 1, 1, 0, 1, 0, 0};
-constexpr int PB[22] = {0, 1, 1, 1, 1, 0, 1, 0, 0, 1, 0, 0, 0, 0, 1, 1, 0, 1, 1, 1, 0, 0};
-constexpr int YB[38] = {1, 1, 0, 0, 0, 0, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 1, 1, 1,
-                        0, 1, 0, 0, 1, 1, 1, 0, 0, 0, 0, 0, 1, 1, 0, 0, 1, 1, 1};
-constexpr uint64_t W_HEAD = packb(QB + 10, 12), W_TAIL = packb(QB, 10), W_N = packb(NB, 22), W_P = packb(PB, 22),
-                   W_Y = packb(YB, 38);
-
 // up to 32 stream bits from pos, from the 32-bit view of the words: one funnel shift
 __device__ __forceinline__ uint32_t bits32_at(const uint32_t *w, int pos) {
     const int q = pos >> 5;
@@ -53,31 +32,8 @@ __device__ __forceinline__ uint32_t bits32_at(const uint32_t *w, int pos) {
 __device__ __forceinline__ int matches32(uint32_t v, uint32_t pat, int len) {
     return len - __popc((v ^ pat) & (len == 32 ? 0xFFFFFFFFu : ((1u << len) - 1)));
 }
-__device__ __forceinline__ int punct_index(int j1) {   // rate 2/3, t=3, P=(1,2,5); 1-based
-    const int g = (j1 - 1) / 3;
-    const int r = j1 - 3 * g;
-    return 8 * g + (r == 1 ? 1 : r == 2 ? 2 : 5);
-}
 
 constexpr int LMAC_MAXBITS = 2 * 2048;
-
-// CRC-16 register as a linear function of the bits (GF(2)): reg(L bits) = INIT[L] ^ XOR over
-// 1-bits at distance d from the end of T[d].  Lets the serial traceback, which emits bits last
-// to first, check the CRC on the fly instead of a second serial pass.
-struct CrcTab {
-    uint32_t t[288];   // dwords: read with wave-uniform scalar loads
-    uint32_t init[289];
-};
-constexpr uint32_t crc_step(uint32_t r) { return ((r & 0x8000u) ? ((r << 1) ^ 0x1021u) : (r << 1)) & 0xFFFFu; }
-constexpr CrcTab make_crc_tab() {
-    CrcTab c{};
-    uint32_t r = crc_step(0x8000u);
-    for (int d = 0; d < 288; ++d) { c.t[d] = r; r = crc_step(r); }
-    uint32_t s = 0xFFFFu;
-    for (int L = 0; L <= 288; ++L) { c.init[L] = s; s = crc_step(s); }
-    return c;
-}
-__constant__ CrcTab CRC_TAB = make_crc_tab();
 
 // --------------------------------------------------------------------------- E3 burst sync
 struct Job {
@@ -592,8 +548,6 @@ __global__ __launch_bounds__(64) void k_etsi_traceback(const Job *__restrict__ j
 // the scrambling init (ecc << 2) | 3 (§8.2.5.2).  Without one the channel keeps its init.  The
 // channel's 432 scrambler bytes (the table k_etsi_viterbi descrambles with) are regenerated only
 // when the init differs from the one the table was made for (tab_init; 0 = none yet).
-constexpr uint32_t SCR_TAPS = (1u << 0) | (1u << 6) | (1u << 9) | (1u << 10) | (1u << 16) | (1u << 20) | (1u << 21) |
-                              (1u << 22) | (1u << 24) | (1u << 25) | (1u << 27) | (1u << 28) | (1u << 30) | (1u << 31);
 
 __global__ __launch_bounds__(256) void k_cell_acquire(int C, const int32_t *__restrict__ nburst,
                                                       const int32_t *__restrict__ bursts,
@@ -638,23 +592,6 @@ __global__ __launch_bounds__(256) void k_cell_acquire(int C, const int32_t *__re
 // The scrambler is linear over GF(2): with x[0..31] the init's bits and x[n + 32] = XOR over the
 // taps t of x[n + t], its output bit n is x[n + 32] = parity(init & SCR_MASK.w[n]).  The table lets
 // a wave form all 432 bits at once (a lane four of them) where k_cell_acquire steps the register.
-struct ScrMask {
-    alignas(16) uint32_t w[432];
-};
-constexpr ScrMask make_scr_mask() {
-    ScrMask m{};
-    uint32_t x[32 + 432] = {};
-    for (int i = 0; i < 32; ++i) x[i] = 1u << i;
-    for (int n = 0; n < 432; ++n) {
-        uint32_t v = 0;
-        for (int t = 0; t < 32; ++t)
-            if ((SCR_TAPS >> t) & 1u) v ^= x[n + t];
-        x[n + 32] = v;
-        m.w[n] = v;
-    }
-    return m;
-}
-__constant__ ScrMask SCR_MASK = make_scr_mask();
 
 // One WAVE per group of G rows (tetra_lmac_etsi_acquire_groups), after the BSCH blocks of every row
 // are decoded: k_cell_acquire's rule over the group's rows in ascending order and each row's bursts

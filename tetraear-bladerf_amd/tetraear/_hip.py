@@ -79,6 +79,9 @@ SLOT_TN, SLOT_FN, SLOT_MN, SLOT_FLAGS, SLOT_FIELDS = range(5)
  PDU_HDR_BITS, PDU_FLAGS) = range(12)
 (PDU_RESOURCE, PDU_FRAG, PDU_END, PDU_SYSINFO, PDU_ACCESS_DEFINE, PDU_BROADCAST, PDU_SUPPL, PDU_SYNC,
  PDU_NULL) = range(9)
+# tetra_etsi_link_quality (include/tetra_hip.h): block records kq and burst records bq
+LQ_NERR, LQ_WERR, LQ_WSUM, LQ_NZERO, LQ_FIELDS = range(5)
+BQ_TERR, BQ_HERR, BQ_WSUM, BQ_NSAT = range(4)
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -150,6 +153,8 @@ def _bind(L):
         "tetra_etsi_mac": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "tetra_etsi_mac_groups": (_i32, [_vp, _vp, _sz, _sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "tetra_etsi_link_quality": (_i32, [_vp, _vp, _vp, _sz, _sz, ctypes.c_int32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp]),
         "tetra_etsi_mix": (_i32, [_vp, _vp, _sz, _sz, _sz, _vp, ctypes.c_double, ctypes.c_int64, _vp]),
         "tetra_etsi_decode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
         "tetra_etsi_encode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp]),

@@ -88,7 +88,8 @@ def _bits_u8(bits):
 class TetraDecoder:
     """Decodes TETRA frames from demodulated symbols (decoder.py:16)."""
 
-    def __init__(self, key_manager=None, auto_decrypt: bool = True, mode=None, mac: bool = False):
+    def __init__(self, key_manager=None, auto_decrypt: bool = True, mode=None, mac: bool = False,
+                 link_quality: bool = False):
         self.SYNC_PATTERN = [0, 1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0,
                              1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0]
         self.FRAME_LENGTH = 510
@@ -101,6 +102,7 @@ class TetraDecoder:
         self.mode = demod_mode(mode)
         self._etsi = None
         self.etsi_mac = bool(mac)   # mode="etsi": TDMA timebase + MAC PDU headers on the frames (EtsiLowerMac(mac=True))
+        self.etsi_link_quality = bool(link_quality)   # mode="etsi": burst and block quality figures on the frames
 
     # ------------------------------------------------------------------ keys and the reference's rest
     def set_keys(self, keys):
@@ -395,6 +397,8 @@ class TetraDecoder:
             self.protocol_parser.count_burst(crc_ok)
             frame.update(burst_crc=crc_ok, blocks=f["blocks"], burst=f["burst"], burst_kind=f["burst_kind"])
             frame.update({k: f[k] for k in ("tn", "fn", "mn", "slot_flags") if k in f})   # EtsiLowerMac(mac=True)
+            frame.update({k: f[k] for k in ("training_errors", "edge_errors", "soft_sum", "saturated")
+                          if k in f})   # EtsiLowerMac(link_quality=True); the blocks carry theirs
             while k < len(owner) and owner[k] == i:   # the MAC state advances in block order
                 pdu = self.protocol_parser.mac_state(fields[k], data[k])
                 if pdu is not None:
@@ -415,5 +419,5 @@ class TetraDecoder:
     def _etsi_rx(self):
         if self._etsi is None:
             from tetraear.core.etsi import EtsiLowerMac
-            self._etsi = EtsiLowerMac(mac=self.etsi_mac)
+            self._etsi = EtsiLowerMac(mac=self.etsi_mac, link_quality=self.etsi_link_quality)
         return self._etsi

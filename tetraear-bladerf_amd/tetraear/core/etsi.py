@@ -9,6 +9,9 @@ This module decodes what the north star asks for (EN 300 392-2 §8.2, §9.4.4):
 The work runs in tetra_lmac_etsi (k_lmac_etsi); this module packages results as frame dicts.
 With ``mac=True`` tetra_etsi_mac (k_etsi_mac) follows it on the device: the TDMA timeslot / frame /
 multiframe of every burst and the MAC PDU headers of every CRC-good block (EN 300 392-2 §21.4).
+With ``link_quality=True`` tetra_etsi_link_quality (k_etsi_quality) follows it too: per burst the known
+bits that came out wrong and the soft bits' strength, per CRC-good block the channel bits the decoder
+corrected.
 """
 import numpy as np
 
@@ -17,6 +20,7 @@ from tetraear import _hip
 BLOCK_NAMES = {0: "SCH/F", 1: "SCH/HD", 2: "BSCH"}
 BURST_NAMES = {0: "NDB (n)", 1: "NDB (p)", 2: "SB"}
 KIND_N1 = {0: 268, 1: 124, 2: 60}
+KIND_K = {0: 432, 1: 216, 2: 120}   # coded (type-5) bits
 
 
 def scrambling_init(mcc, mnc, colour_code):
@@ -76,6 +80,53 @@ def acquired_channels(nblock, blocks):
     return np.any(live & (blocks[:, :, 0] == 2) & (blocks[:, :, 1] != 0), axis=1)
 
 
+def run_link_quality(c, soft, hard, origin, G, cells, nb, bursts, nk, blocks, t1):
+    """tetra_etsi_link_quality on host arrays: (bq [C, MAXB, 4], kq [C, MAXJ, 4]), -1 where not written."""
+    C, stride = hard.shape
+    cells = np.ascontiguousarray(cells, np.uint32)
+    bq = np.full((C, _hip.ETSI_MAXB, _hip.LQ_FIELDS), -1, np.int32)
+    kq = np.full((C, _hip.ETSI_MAXJ, _hip.LQ_FIELDS), -1, np.int32)
+    c.check(c.lib.tetra_etsi_link_quality(c.handle, _hip.ptr(soft), _hip.ptr(hard), C, stride, origin, G,
+                                          _hip.ptr(cells), _hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk),
+                                          _hip.ptr(blocks), _hip.ptr(t1), _hip.ptr(bq), _hip.ptr(kq)),
+            "tetra_etsi_link_quality")
+    return bq, kq
+
+
+def burst_quality(rec):
+    """One burst record of tetra_etsi_link_quality as the keys a frame gains (None: not scored)."""
+    r = [int(v) if v >= 0 else None for v in rec]
+    return {"training_errors": r[_hip.BQ_TERR], "edge_errors": r[_hip.BQ_HERR], "soft_sum": r[_hip.BQ_WSUM],
+            "saturated": r[_hip.BQ_NSAT]}
+
+
+def block_quality(rec, kind):
+    """One block record as the keys a block gains; channel_errors and ber are None for a CRC-bad block."""
+    r = [int(v) for v in rec]
+    scored = r[_hip.LQ_NERR] >= 0
+    n = KIND_K[kind] - r[_hip.LQ_NZERO]
+    return {"channel_errors": r[_hip.LQ_NERR] if scored else None, "channel_bits": KIND_K[kind],
+            "soft_errors": r[_hip.LQ_WERR] if scored else None, "soft_sum": r[_hip.LQ_WSUM] if scored else None,
+            "erased": r[_hip.LQ_NZERO] if scored else None,
+            "ber": r[_hip.LQ_NERR] / n if scored and n > 0 else None}
+
+
+def carrier_quality(frames):
+    """Per-carrier totals of link_quality frames (one list of frames per carrier, as decode_batch or
+    the wideband receiver returns them): [dict(blocks, blocks_ok, channel_errors, channel_bits, ber)],
+    channel_bits counting the CRC-good blocks' bits that were not erased and ber = channel_errors /
+    channel_bits (None when no block decoded).  A scanner ranks carriers by blocks_ok and ber."""
+    out = []
+    for fr in frames:
+        blks = [b for f in fr for b in f["blocks"]]
+        good = [b for b in blks if b.get("channel_errors") is not None]
+        err = sum(b["channel_errors"] for b in good)
+        bits = sum(b["channel_bits"] - b["erased"] for b in good)
+        out.append({"blocks": len(blks), "blocks_ok": len(good), "channel_errors": err, "channel_bits": bits,
+                    "ber": err / bits if bits else None})
+    return out
+
+
 class EtsiLowerMac:
     """Lower MAC of the ETSI chain.  With a cell (mcc, mnc, colour_code) every channel is
     descrambled with it.  Without one the receiver acquires the cell itself: each chunk's BSCH
@@ -89,10 +140,20 @@ class EtsiLowerMac:
     (None while the channel has no timebase) and ``slot_flags``, every block ``pdus`` (dicts of the
     first TETRA_ETSI_MAXPDU MAC PDU headers, pdu_dict) and ``npdu``.  The timebase is carried from
     chunk to chunk by decode_stream / decode (reset_stream() drops it) and is fresh for every
-    decode_batch.  Without it the frames are unchanged."""
+    decode_batch.  Without it the frames are unchanged.
 
-    def __init__(self, mcc=None, mnc=None, colour_code=None, mac=False):
+    ``link_quality=True``: tetra_etsi_link_quality runs after the lower MAC on the rows it read.  Every
+    frame gains ``training_errors`` / ``edge_errors`` (training-sequence and head / tail bits that came
+    out wrong), ``soft_sum`` (sum of |soft| over the burst's 510 bits) and ``saturated`` (soft bits at
+    full scale); every block ``channel_errors`` (coded bits the decoder corrected, None when the CRC
+    failed), ``channel_bits``, ``soft_errors`` (sum of |soft| over the corrected bits), ``soft_sum``,
+    ``erased`` (soft bits at 0) and ``ber`` = channel_errors / (channel_bits - erased).  decode_stream
+    then alternates two sets of rows, so the rows a call read are intact for the quality pass.
+    Everything else in the frames is unchanged."""
+
+    def __init__(self, mcc=None, mnc=None, colour_code=None, mac=False, link_quality=False):
         self.mac = bool(mac)
+        self.link_quality = bool(link_quality)
         self.acquire = mcc is None and mnc is None and colour_code is None
         self.cell = None if self.acquire else scrambling_init(mcc or 0, mnc or 0, colour_code or 0)
         self.cell_state = None   # [C] scrambling inits of the acquired cells (acquisition mode)
@@ -104,6 +165,7 @@ class EtsiLowerMac:
     def reset_stream(self):
         """decode_stream / decode start a new capture: no carried dibits."""
         self._rows = None   # (soft rows [C, 2 stride], hard rows [C, stride], lead [C]): the carried tails
+        self._alt = None    # link_quality: the other (soft rows, hard rows), which the next tails go to
         self._tdma = None   # [C] tetra_etsi_tdma: the carried timebases (mac=True)
 
     @property
@@ -152,6 +214,7 @@ class EtsiLowerMac:
                                                   _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
                     "tetra_lmac_etsi_acquire")
             self.acquired |= acquired_channels(nk, blocks)
+            used = self.cell_state
         else:
             cells = np.full(C, self.cell if self.cell is not None else UNKNOWN_CELL, np.uint32) if cells is None \
                 else np.ascontiguousarray(cells, np.uint32)
@@ -159,7 +222,17 @@ class EtsiLowerMac:
             c.check(c.lib.tetra_lmac_etsi(c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(nsym), C, smax,
                                           _hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
                     "tetra_lmac_etsi")
-        return self._frames(C, nb, bursts, nk, blocks, t1, self._run_mac(c, C, nsym, nb, bursts, nk, blocks, t1, None))
+            used = cells
+        lq = self._run_quality(c, soft, hard, 0, used, nb, bursts, nk, blocks, t1)
+        return self._frames(C, nb, bursts, nk, blocks, t1, self._run_mac(c, C, nsym, nb, bursts, nk, blocks, t1, None),
+                            lq)
+
+    def _run_quality(self, c, soft, hard, origin, cells, nb, bursts, nk, blocks, t1):
+        """tetra_etsi_link_quality on the rows the lower-MAC call read (link_quality=True; else None):
+        (bq, kq).  cells [C]: the inits the rows were descrambled with."""
+        if not self.link_quality:
+            return None
+        return run_link_quality(c, soft, hard, origin, 1, cells, nb, bursts, nk, blocks, t1)
 
     def _run_mac(self, c, C, nsym, nb, bursts, nk, blocks, t1, tdma):
         """tetra_etsi_mac on the lower MAC's outputs (mac=True; else None): (slots, npdu, pdus).
@@ -177,8 +250,9 @@ class EtsiLowerMac:
         return slots, npdu, pdus
 
     def _run_stream(self, c, C, nb, bursts, nk, blocks, t1, cells, stream):
-        """tetra_lmac_etsi_stream over stream = (soft rows, hard rows, nsym, stride, lead), with the
-        receiver's cell handling (acquisition state or configured cells) as decode_batch's."""
+        """tetra_lmac_etsi_stream over stream = (soft rows, hard rows, nsym, stride, lead[, next soft
+        rows, next hard rows]), with the receiver's cell handling (acquisition state or configured
+        cells) as decode_batch's.  Returns the inits the rows were descrambled with."""
         if self.acquire and cells is None:
             if self.cell_state is None or len(self.cell_state) != C:
                 self.cell_state = np.full(C, UNKNOWN_CELL, np.uint32)
@@ -191,13 +265,16 @@ class EtsiLowerMac:
                 else np.ascontiguousarray(cells, np.uint32)
             c.check(c.lib.tetra_etsi_set_cells(c.handle, _hip.ptr(cells), C), "tetra_etsi_set_cells")
             ci = None
-        srow, hrow, ns, stride, lead = stream
+        srow, hrow, ns, stride, lead = stream[:5]
+        nsrow, nhrow = stream[5:] if len(stream) > 5 else (srow, hrow)
         c.check(c.lib.tetra_lmac_etsi_stream(c.handle, _hip.ptr(srow), _hip.ptr(hrow), _hip.ptr(ns), C, stride,
-                                             _hip.ptr(lead), _hip.ptr(srow), _hip.ptr(hrow), ci, _hip.ptr(nb),
+                                             _hip.ptr(lead), _hip.ptr(nsrow), _hip.ptr(nhrow), ci, _hip.ptr(nb),
                                              _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
                 "tetra_lmac_etsi_stream")
         if ci is not None:
             self.acquired |= acquired_channels(nk, blocks)
+            return self.cell_state
+        return cells
 
     def decode_stream(self, soft, hard, nsym, cells=None):
         """decode_batch for consecutive chunks of C continuous streams (EtsiStream.demod rows):
@@ -219,8 +296,11 @@ class EtsiLowerMac:
                 srow[:, :2 * R], hrow[:, :R] = self._rows[0][:, :2 * R], self._rows[1][:, :R]
                 lead = self._rows[2]
             self._rows = (srow, hrow, lead)
+            self._alt = None
         srow, hrow, lead = self._rows
         stride = hrow.shape[1]
+        if self.link_quality and self._alt is None:
+            self._alt = (np.zeros_like(srow), np.zeros_like(hrow))
         hrow[:, R:R + smax] = hard
         srow[:, 2 * R:2 * R + 2 * smax] = soft
         nb = np.zeros(C, np.int32)
@@ -228,15 +308,22 @@ class EtsiLowerMac:
         nk = np.zeros(C, np.int32)
         blocks = np.zeros((C, _hip.ETSI_MAXJ, 4), np.int32)
         t1 = np.zeros((C, _hip.ETSI_MAXJ, 268), np.uint8)
-        self._run_stream(_hip.ctx(), C, nb, bursts, nk, blocks, t1, cells, (srow, hrow, nsym, stride, lead))
+        # link_quality: the tails go to the other rows, these stay as the call read them
+        nxt = self._alt if self.link_quality else ()
+        used = self._run_stream(_hip.ctx(), C, nb, bursts, nk, blocks, t1, cells,
+                                (srow, hrow, nsym, stride, lead) + tuple(nxt))
+        lq = self._run_quality(_hip.ctx(), srow, hrow, 2 * R, used, nb, bursts, nk, blocks, t1)
+        if self.link_quality:
+            self._rows, self._alt = (nxt[0], nxt[1], lead), (srow, hrow)
         if self.mac and (self._tdma is None or len(self._tdma) != C):
             self._tdma = np.zeros(C, _hip.ETSI_TDMA)
         return self._frames(C, nb, bursts, nk, blocks, t1,
-                            self._run_mac(_hip.ctx(), C, nsym, nb, bursts, nk, blocks, t1, self._tdma))
+                            self._run_mac(_hip.ctx(), C, nsym, nb, bursts, nk, blocks, t1, self._tdma), lq)
 
     @staticmethod
-    def _frames(C, nb, bursts, nk, blocks, t1, mac=None):
-        """mac: None, or tetra_etsi_mac's (slots, npdu, pdus) for the same call."""
+    def _frames(C, nb, bursts, nk, blocks, t1, mac=None, lq=None):
+        """mac: None, or tetra_etsi_mac's (slots, npdu, pdus) for the same call; lq: None, or
+        tetra_etsi_link_quality's (bq, kq)."""
         out = []
         for ch in range(C):
             frames = []
@@ -252,6 +339,8 @@ class EtsiLowerMac:
                     if mac is not None:
                         n = int(mac[1][ch, j])
                         blks[-1].update(npdu=n, pdus=[pdu_dict(r) for r in mac[2][ch, j, :min(n, _hip.ETSI_MAXPDU)]])
+                    if lq is not None:
+                        blks[-1].update(block_quality(lq[1][ch, j], k))
                 frames.append({"position": start, "burst": BURST_NAMES[kind], "burst_kind": kind,
                                "timeslot": (start // 510) % 4, "blocks": blks,
                                "crc_ok": all(x["crc_ok"] for x in blks)})
@@ -260,6 +349,8 @@ class EtsiLowerMac:
                     known = tn != 0
                     frames[-1].update(tn=tn if known else None, fn=fn if known else None, mn=mn if known else None,
                                       slot_flags=fl)
+                if lq is not None:
+                    frames[-1].update(burst_quality(lq[0][ch, b]))
             out.append(frames)
         return out
 

@@ -230,7 +230,7 @@ class WidebandReceiver:
                 ns.reshape(M, ck.nchunk))
 
 
-    def decode(self, x, cells, mac=False, timebase=False, tol=64):
+    def decode(self, x, cells, mac=False, timebase=False, tol=64, link_quality=False):
         """x [Nw] -> per carrier the frames decoded from it, each burst once (merge_chunks), in row
         order: demod, then the ETSI lower MAC on every (carrier, chunk) with carrier k's scrambling
         init cells[k].  A frame is the lower MAC's dict (core/etsi.py) plus "chunk" and "sample" (its
@@ -241,26 +241,30 @@ class WidebandReceiver:
         timebase per carrier over them, a new stream per call: every frame gains ``tn`` / ``fn`` /
         ``mn`` / ``slot_flags`` as EtsiLowerMac's frames carry them (None before the carrier's first
         CRC-good SYNC).  tol: the duplicate distance in 72 kHz samples (merge_chunks'); timebase=True
-        needs it and m2 even (the device works in bits), else ValueError."""
-        return self._decode(x, np.asarray(cells, np.uint32), None, mac, timebase, tol)[0]
+        needs it and m2 even (the device works in bits), else ValueError.  link_quality=True: the
+        frames and blocks gain EtsiLowerMac(link_quality=True)'s keys, from one tetra_etsi_link_quality
+        call over all (carrier, chunk) rows with G = chunks per carrier (core/etsi.py carrier_quality
+        totals them per carrier)."""
+        return self._decode(x, np.asarray(cells, np.uint32), None, mac, timebase, tol, link_quality=link_quality)[0]
 
-    def decode_acquire(self, x, cell_init, mac=False, timebase=False, tol=64):
+    def decode_acquire(self, x, cell_init, mac=False, timebase=False, tol=64, link_quality=False):
         """decode without given cells: cell_init [M] holds each carrier's scrambling init before the
         capture (3 = unknown); every carrier's cell comes from the last CRC-good BSCH over all of its
         chunk rows, and all of its rows are descrambled with it (tetra_lmac_etsi_acquire_groups, G =
         chunks per carrier).  Returns (frames as decode's, the inits after the capture [M] uint32,
-        ngood [M] int32: the CRC-good BSCH blocks seen per carrier, copies in two chunks counted twice)."""
+        ngood [M] int32: the CRC-good BSCH blocks seen per carrier, copies in two chunks counted twice).
+        link_quality=True scores every carrier's blocks with the cell acquired for it."""
         state = np.array(cell_init, np.uint32)
         if state.shape != (self.plan.M,):
             raise ValueError(f"cell_init holds {state.shape} inits, the receiver has {self.plan.M} carriers")
-        frames, ngood = self._decode(x, None, state, mac, timebase, tol)
+        frames, ngood = self._decode(x, None, state, mac, timebase, tol, link_quality=link_quality)
         return frames, state, ngood
 
-    def _decode(self, x, cells, state, mac, timebase=False, tol=64, tdma=None, advance=0):
+    def _decode(self, x, cells, state, mac, timebase=False, tol=64, tdma=None, advance=0, link_quality=False):
         """The chain behind decode (cells [M]) and decode_acquire (state [M], updated in place):
         (frames, ngood or None).  timebase: tdma [M] ETSI_TDMA (in/out; None: new streams), whose bit0
         moves on by ``advance`` bits after the call (WidebandStream)."""
-        from tetraear.core.etsi import EtsiLowerMac
+        from tetraear.core.etsi import EtsiLowerMac, run_link_quality
         if timebase and (self.m2 % 2 or tol % 2 or tol < 0):
             raise ValueError(f"timebase=True works in bits: m2 ({self.m2}) and tol ({tol}) must be even")
         hard, soft, _, ns = self.demod(x)
@@ -301,7 +305,11 @@ class WidebandReceiver:
         if mac and not timebase:   # the PDU walk is per block; a fresh timebase per row, its slots not reported
             pdus = EtsiLowerMac(mac=True)._run_mac(c, C, np.ascontiguousarray(ns.reshape(-1)), nb, bursts, nk, blocks,
                                                   t1, None)
-        frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1, pdus)
+        lq = None
+        if link_quality:   # the rows are intact (origin 0); carrier k's rows with its (acquired) cell
+            lq = run_link_quality(c, soft.reshape(C, -1), hard.reshape(C, -1), 0, nchunk,
+                                  cells if state is None else state, nb, bursts, nk, blocks, t1)
+        frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1, pdus, lq)
         if mac and not timebase:
             for fr in frames:
                 for f in fr:
@@ -341,6 +349,7 @@ class WidebandStream:
     (implies it): the frames carry ``tn`` / ``fn`` / ``mn`` / ``slot_flags`` from one TDMA timebase per
     carrier, carried from piece to piece in ``tdma`` [M] (reset() clears it): a buffer's carried tail
     is decoded again behind the anchor, which places those bursts without moving it.
+    ``link_quality=True``: the frames and blocks carry the link-quality keys (WidebandReceiver.decode).
 
     The pieces may be [n, 2] int16 (SC16, a recording or the radio's buffer as it is): the tail is
     then kept in int16 and the buffer goes to the device in 4 B per sample.  If the pieces change
@@ -348,9 +357,11 @@ class WidebandStream:
     complex64, so a mixed stream gives what the complex64 stream does."""
     CARRY_Y = 2 * BURST_SAMPLES
 
-    def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False, timebase=False):
+    def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False, timebase=False,
+                 link_quality=False):
         self.rx = WidebandReceiver(fs, M, m2, oversample)
         self.acquire, self.mac, self.timebase = cells is None, bool(mac), bool(timebase)
+        self.link_quality = bool(link_quality)
         if self.timebase and m2 % 2:
             raise ValueError(f"timebase=True works in bits: m2 ({m2}) must be even")
         self._cells = None if self.acquire else np.ascontiguousarray(cells, np.uint32)
@@ -382,12 +393,15 @@ class WidebandStream:
     def _decode_buffer(self, buf, advance=0):
         if self.timebase:
             state = np.array(self.cell_state, np.uint32) if self.acquire else None
-            frames, ngood = self.rx._decode(buf, self._cells, state, True, True, 64, self.tdma, advance)
+            frames, ngood = self.rx._decode(buf, self._cells, state, True, True, 64, self.tdma, advance,
+                                            link_quality=self.link_quality)
             if self.acquire:
                 self.cell_state = state
                 self.acquired |= ngood > 0
             return frames
         kw = {"mac": True} if self.mac else {}
+        if self.link_quality:
+            kw["link_quality"] = True
         if not self.acquire:
             return self.rx.decode(buf, self._cells, **kw)
         frames, self.cell_state, ngood = self.rx.decode_acquire(buf, self.cell_state, **kw)
