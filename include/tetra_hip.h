@@ -491,6 +491,57 @@ int tetra_lmac_etsi_stream(tetra_ctx *ctx, const int8_t *softbits, const uint8_t
                            uint32_t *cell_init, int32_t *nburst, int32_t *bursts, int32_t *nblock, int32_t *blocks,
                            uint8_t *type1);
 
+/* ---------------------------------------------------------------- cell vote (new symbols of ABI version 2;
+ * nothing existing changed shape).  tetra_lmac_etsi_acquire and _acquire_groups let the LAST CRC-good BSCH
+ * set a cell: one false CRC pass on a badly received block (2^-16 per failed block), or a neighbour
+ * cell's synchronisation burst heard on the carrier, replaces the cell, and every SCH block after it is
+ * descrambled wrongly until the next good BSCH.  The vote entry points are those calls with every
+ * CRC-good BSCH weighed by its soft bits and the cell kept so far defending with a score.
+ *
+ * The rule (exact integers).  State per group g of G rows: cell_init[g] (uint32, in/out, as above; 3 =
+ * unknown) and score[g] (int32, in/out; 0 = fresh; a negative value is read as 0).
+ *   Ballots: the group's CRC-good BSCH blocks in order -- rows ascending, each row's bursts in order (the
+ *     blocks ngood counts).  Block i has c_i, the init from its type-1 bits (the fields of
+ *     tetra_lmac_etsi_acquire), and w_i = max(1, WSUM_i - 2 WERR_i), where WSUM and WERR are
+ *     tetra_etsi_link_quality's block-record quantities for the block: its 60 type-1 bits re-encoded as
+ *     tetra_etsi_encode_blocks does (kind 2, init 3) into 120 type-5 bits and held against the 120 soft
+ *     bytes the trellis read (row bits start + 94 ..., from the streaming origin for streaming rows);
+ *     WSUM = sum of |s| over the 120, WERR = sum of |s| over the non-zero s whose sign disagrees with the
+ *     codeword.  w_i is the correlation of the soft bits with the codeword the decoder chose -- the
+ *     Viterbi's own path metric, no tuned constant -- at most 120 * 127 = 15240 for soft bits in
+ *     [-127, 127].
+ *   Totals (int64): T(c) = sum of w_i over c_i == c, plus score[g] if c == cell_init[g].  Candidates: the
+ *     incoming cell_init[g] and every distinct c_i.
+ *   Winner: the largest T; on a tie the incoming cell if it is among the tied, else the tied candidate
+ *     whose last ballot comes latest.
+ *   Update: without a ballot cell_init[g] and score[g] stay as they were; else cell_init[g] = winner and
+ *     score[g] = min(cap, max(1, T(winner) - sum of T(c) over c != winner)): a weighted majority vote of
+ *     Boyer-Moore type -- losers wear the incumbent down -- and cap (> 0) bounds incumbency, so a real
+ *     change of cell wins after a bounded amount of contrary evidence.
+ *   Outputs: ngood[g] = the number of ballots, agree[g] = the ballots with c_i == winner (0 without one).
+ * With score 0 and one ballot this is tetra_lmac_etsi_acquire_groups's rule.  Every SCH/F and SCH/HD
+ * block of every row of the group is then descrambled with cell_init[g], exactly as there.  A burst in
+ * samples that two overlapping chunks share votes in both rows, as it counts in ngood twice.
+ * TETRA_ETSI_VOTE_CAP_DEFAULT: eight full-scale BSCH blocks, about two multiframes of frame-18
+ * broadcasts at full strength -- a stated choice, not a measurement. */
+#define TETRA_ETSI_VOTE_CAP_DEFAULT 121920
+/* tetra_lmac_etsi_acquire_groups with the vote: score [C / G] in/out and agree [C / G] out beside
+ * cell_init and ngood, host or device.  TETRA_E_INVALID with nothing written: a NULL cell_init, score,
+ * ngood or agree, cap <= 0, G == 0, C % G != 0, G > 32 (a group's ballot list is fixed-size;
+ * tetra_lmac_etsi_acquire_groups keeps serving larger groups), and whatever tetra_lmac_etsi refuses. */
+int tetra_lmac_etsi_vote_groups(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym,
+                                size_t C, size_t smax, size_t G, int32_t cap, uint32_t *cell_init /*[C/G] in/out*/,
+                                int32_t *score /*[C/G] in/out*/, int32_t *ngood /*[C/G] out*/,
+                                int32_t *agree /*[C/G] out*/, int32_t *nburst, int32_t *bursts, int32_t *nblock,
+                                int32_t *blocks, uint8_t *type1);
+/* tetra_lmac_etsi_stream in acquisition mode with the vote, a group being one streaming row: cell_init
+ * [C] and score [C] in/out (NULL: TETRA_E_INVALID, as cap <= 0), agree [C] out (may be NULL).  A BSCH that
+ * began in the carried tail votes in the call that decodes it, with the soft bytes carried with it. */
+int tetra_lmac_etsi_stream_vote(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym,
+                                size_t C, size_t stride, int32_t *lead, int8_t *next_soft, uint8_t *next_hard,
+                                int32_t cap, uint32_t *cell_init, int32_t *score, int32_t *agree, int32_t *nburst,
+                                int32_t *bursts, int32_t *nblock, int32_t *blocks, uint8_t *type1);
+
 /* ---------------------------------------------------------------- TDMA timebase + MAC PDU headers
  * What a receiver reads next from the lower MAC's outputs, on the device: per burst the TDMA
  * timeslot / frame / multiframe, per CRC-good block the headers of its MAC PDUs, as small int32

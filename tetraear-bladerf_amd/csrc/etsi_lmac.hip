@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "etsi_coding.h"   // block kinds, burst patterns, puncturer, CRC and scrambler tables
+#include "etsi_vote.h"     // the cell vote's launch (etsi_vote.hip)
 
 namespace {
 
@@ -856,10 +857,13 @@ int tetra_etsi_encode_blocks(tetra_ctx *ctx, const uint8_t *type1, size_t F, int
 
 // The lower MAC's launch sequence; cell_init (device) selects acquisition, else the configured cells.
 // G > 0 (with ngood): acquisition per group of G rows, cell_init and ngood C / G long.
+// score (with cap; agree may be null): the vote (etsi_vote.hip) in place of the last-good-BSCH kernels,
+// over groups of G rows, or of one row where G == 0; score and agree as long as cell_init.
 static int lmac_etsi(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym, size_t C,
                      size_t smax, uint32_t *cell_init, int32_t *nburst, int32_t *bursts, int32_t *nblock,
                      int32_t *blocks, uint8_t *type1, int32_t *lead = nullptr, int8_t *next_soft = nullptr,
-                     uint8_t *next_hard = nullptr, size_t G = 0, int32_t *ngood = nullptr) {
+                     uint8_t *next_hard = nullptr, size_t G = 0, int32_t *ngood = nullptr, int32_t *score = nullptr,
+                     int32_t cap = 0, int32_t *agree = nullptr) {
     if (!ctx || C == 0) return TETRA_E_INVALID;
     const size_t ncell = G ? C / G : C;   // acquisition states
     if (!cell_init && ctx->cells < C)
@@ -871,6 +875,19 @@ static int lmac_etsi(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard
     Staging st(ctx);
     uint32_t *ci = cell_init ? (uint32_t *)st.inout(cell_init, ncell * 4) : nullptr;
     int32_t *ngo = G ? (int32_t *)st.out(ngood, ncell * 4) : nullptr;
+    // the vote's score (in/out) and agree (out): host arrays travel as one staged buffer (the streaming
+    // form stages nine outputs already)
+    int32_t *sco = score, *ago = agree;
+    std::vector<int32_t> small;
+    const bool hs = score && !is_device_ptr(score), ha = agree && !is_device_ptr(agree);
+    if (hs || ha) {
+        small.assign((hs ? ncell : 0) + (ha ? ncell : 0), 0);
+        if (hs) memcpy(small.data(), score, ncell * 4);
+        int32_t *d = (int32_t *)st.inout(small.data(), small.size() * 4);
+        if (!d) return st.finish();
+        if (hs) sco = d;
+        if (ha) ago = d + (hs ? ncell : 0);
+    }
     // streaming into the input rows themselves: host rows are staged in and back out (with the tail)
     const bool alias = lead && next_soft == softbits;
     const int8_t *sb = alias ? (const int8_t *)st.inout(const_cast<int8_t *>(softbits), C * smax * 2)
@@ -939,7 +956,10 @@ static int lmac_etsi(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard
         hipLaunchKernelGGL(k_etsi_viterbi, vgrid(4), dim3(64), 0, ctx->stream, jobs, jcount, (int)C, sb, (int)smax,
                            cells, bsch_scr, surv, 4);
         hipLaunchKernelGGL(k_etsi_traceback, tgrid(4), dim3(64), 0, ctx->stream, jobs, jcount, (int)C, surv, ko, to, 4);
-        if (G)
+        if (sco)
+            launch_cell_vote(ctx, ncell, G ? G : 1, sb, 2 * smax, lead ? 2 * TETRA_ETSI_RESERVE : 0, nbo, bo, ko, to, ci,
+                             sco, cap, ngo, ago, (uint32_t *)ctx->slot[S_W14].p, cells);
+        else if (G)
             hipLaunchKernelGGL(k_cell_acquire_groups, dim3(grid_for(ncell, ACQ_WAVES)), dim3(64 * ACQ_WAVES), 0,
                                ctx->stream, (int)ncell, (int)G, nbo, bo, ko, to, ci, ngo,
                                (uint32_t *)ctx->slot[S_W14].p, cells);
@@ -963,7 +983,10 @@ static int lmac_etsi(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard
         hipLaunchKernelGGL(k_etsi_tail, dim3((unsigned)C), dim3(64), 0, ctx->stream, hd, sb, (int)smax, (int)C, tinfo,
                            TETRA_ETSI_RESERVE, nhd, nsb, ld_);
     }
-    return st.finish();
+    const int rc = st.finish();
+    if (rc == TETRA_OK && hs) memcpy(score, small.data(), ncell * 4);
+    if (rc == TETRA_OK && ha) memcpy(agree, small.data() + (hs ? ncell : 0), ncell * 4);
+    return rc;
 }
 
 int tetra_lmac_etsi(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym, size_t C,
@@ -989,6 +1012,20 @@ int tetra_lmac_etsi_acquire_groups(tetra_ctx *ctx, const int8_t *softbits, const
                      nullptr, nullptr, G, ngood);
 }
 
+int tetra_lmac_etsi_vote_groups(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym,
+                                size_t C, size_t smax, size_t G, int32_t cap, uint32_t *cell_init, int32_t *score,
+                                int32_t *ngood, int32_t *agree, int32_t *nburst, int32_t *bursts, int32_t *nblock,
+                                int32_t *blocks, uint8_t *type1) {
+    if (!cell_init || !score || !ngood || !agree)
+        return tetra_fail(ctx, TETRA_E_INVALID, "lmac_etsi_vote_groups: cell_init, score, ngood or agree is NULL");
+    if (cap <= 0) return tetra_fail(ctx, TETRA_E_INVALID, "lmac_etsi_vote_groups: cap %d is not positive", (int)cap);
+    if (G == 0 || C % G != 0 || G > VOTE_MAXG)
+        return tetra_fail(ctx, TETRA_E_INVALID, "lmac_etsi_vote_groups: %zu rows are not whole groups of %zu (at most %zu)",
+                          C, G, VOTE_MAXG);
+    return lmac_etsi(ctx, softbits, hard, nsym, C, smax, cell_init, nburst, bursts, nblock, blocks, type1, nullptr,
+                     nullptr, nullptr, G, ngood, score, cap, agree);
+}
+
 int tetra_lmac_etsi_stream(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym,
                            size_t C, size_t stride, int32_t *lead, int8_t *next_soft, uint8_t *next_hard,
                            uint32_t *cell_init, int32_t *nburst, int32_t *bursts, int32_t *nblock, int32_t *blocks,
@@ -999,6 +1036,20 @@ int tetra_lmac_etsi_stream(tetra_ctx *ctx, const int8_t *softbits, const uint8_t
         return tetra_fail(ctx, TETRA_E_INVALID, "lmac_etsi_stream: next rows must both alias the inputs or neither");
     return lmac_etsi(ctx, softbits, hard, nsym, C, stride, cell_init, nburst, bursts, nblock, blocks, type1, lead,
                      next_soft, next_hard);
+}
+
+int tetra_lmac_etsi_stream_vote(tetra_ctx *ctx, const int8_t *softbits, const uint8_t *hard, const int32_t *nsym,
+                                size_t C, size_t stride, int32_t *lead, int8_t *next_soft, uint8_t *next_hard,
+                                int32_t cap, uint32_t *cell_init, int32_t *score, int32_t *agree, int32_t *nburst,
+                                int32_t *bursts, int32_t *nblock, int32_t *blocks, uint8_t *type1) {
+    if (!lead || !next_soft || !next_hard || stride <= TETRA_ETSI_RESERVE)
+        return tetra_fail(ctx, TETRA_E_INVALID, "lmac_etsi_stream_vote: lead, next rows and stride > TETRA_ETSI_RESERVE");
+    if ((next_soft == softbits) != (next_hard == hard))
+        return tetra_fail(ctx, TETRA_E_INVALID, "lmac_etsi_stream_vote: next rows must both alias the inputs or neither");
+    if (!cell_init || !score) return tetra_fail(ctx, TETRA_E_INVALID, "lmac_etsi_stream_vote: cell_init or score is NULL");
+    if (cap <= 0) return tetra_fail(ctx, TETRA_E_INVALID, "lmac_etsi_stream_vote: cap %d is not positive", (int)cap);
+    return lmac_etsi(ctx, softbits, hard, nsym, C, stride, cell_init, nburst, bursts, nblock, blocks, type1, lead,
+                     next_soft, next_hard, 0, nullptr, score, cap, agree);
 }
 
 }  // extern "C"

@@ -82,6 +82,9 @@ SLOT_TN, SLOT_FN, SLOT_MN, SLOT_FLAGS, SLOT_FIELDS = range(5)
 # tetra_etsi_link_quality (include/tetra_hip.h): block records kq and burst records bq
 LQ_NERR, LQ_WERR, LQ_WSUM, LQ_NZERO, LQ_FIELDS = range(5)
 BQ_TERR, BQ_HERR, BQ_WSUM, BQ_NSAT = range(4)
+# the cell vote (tetra_lmac_etsi_vote_groups / _stream_vote): the default bound on a cell's score, eight
+# full-scale BSCH blocks (120 x 127 each)
+TETRA_ETSI_VOTE_CAP_DEFAULT = 8 * 120 * 127
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -150,6 +153,10 @@ def _bind(L):
         "tetra_demod_etsi_stream": (_i32, [_vp, ctypes.POINTER(EtsiPlan), _vp, _i32, _sz, _sz, _sz, ctypes.c_int,
                                            _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]),
         "tetra_lmac_etsi_stream": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "tetra_lmac_etsi_vote_groups": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, ctypes.c_int32, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, _vp, _vp]),
+        "tetra_lmac_etsi_stream_vote": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp,
+                                               _vp, _vp, _vp, _vp, _vp, _vp]),
         "tetra_etsi_mac": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "tetra_etsi_mac_groups": (_i32, [_vp, _vp, _sz, _sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

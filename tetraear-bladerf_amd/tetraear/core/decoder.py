@@ -89,7 +89,7 @@ class TetraDecoder:
     """Decodes TETRA frames from demodulated symbols (decoder.py:16)."""
 
     def __init__(self, key_manager=None, auto_decrypt: bool = True, mode=None, mac: bool = False,
-                 link_quality: bool = False):
+                 link_quality: bool = False, vote: bool = False):
         self.SYNC_PATTERN = [0, 1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0,
                              1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0]
         self.FRAME_LENGTH = 510
@@ -103,6 +103,7 @@ class TetraDecoder:
         self._etsi = None
         self.etsi_mac = bool(mac)   # mode="etsi": TDMA timebase + MAC PDU headers on the frames (EtsiLowerMac(mac=True))
         self.etsi_link_quality = bool(link_quality)   # mode="etsi": burst and block quality figures on the frames
+        self.etsi_vote = bool(vote)   # mode="etsi": the cell by the soft-weighted vote (EtsiLowerMac(vote=True))
 
     # ------------------------------------------------------------------ keys and the reference's rest
     def set_keys(self, keys):
@@ -419,5 +420,5 @@ class TetraDecoder:
     def _etsi_rx(self):
         if self._etsi is None:
             from tetraear.core.etsi import EtsiLowerMac
-            self._etsi = EtsiLowerMac(mac=self.etsi_mac, link_quality=self.etsi_link_quality)
+            self._etsi = EtsiLowerMac(mac=self.etsi_mac, link_quality=self.etsi_link_quality, vote=self.etsi_vote)
         return self._etsi

@@ -149,12 +149,26 @@ class EtsiLowerMac:
     failed), ``channel_bits``, ``soft_errors`` (sum of |soft| over the corrected bits), ``soft_sum``,
     ``erased`` (soft bits at 0) and ``ber`` = channel_errors / (channel_bits - erased).  decode_stream
     then alternates two sets of rows, so the rows a call read are intact for the quality pass.
-    Everything else in the frames is unchanged."""
+    Everything else in the frames is unchanged.
 
-    def __init__(self, mcc=None, mnc=None, colour_code=None, mac=False, link_quality=False):
+    ``vote=True`` (acquisition mode only): the cell is chosen by the vote of tetra_lmac_etsi_vote_groups /
+    _stream_vote instead of by the last CRC-good BSCH -- every CRC-good BSCH weighs in with the
+    correlation of its soft bits with its re-encoded codeword, and the cell kept so far defends with
+    ``cell_score`` [C] (int32, kept next to ``cell_state``; reset_stream() clears it), bounded by
+    ``vote_cap``.  One false CRC pass or a neighbour cell's burst then no longer replaces an established
+    cell.  With one cell per channel the frames are those of ``vote=False``."""
+
+    def __init__(self, mcc=None, mnc=None, colour_code=None, mac=False, link_quality=False, vote=False,
+                 vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT):
         self.mac = bool(mac)
         self.link_quality = bool(link_quality)
         self.acquire = mcc is None and mnc is None and colour_code is None
+        self.vote, self.vote_cap = bool(vote), int(vote_cap)
+        if self.vote and not self.acquire:
+            raise ValueError("vote=True chooses among acquired cells: it takes no mcc / mnc / colour_code")
+        if self.vote and self.vote_cap <= 0:
+            raise ValueError(f"vote_cap ({vote_cap}) must be positive")
+        self.cell_score = None   # [C] int32: the score each channel's cell has gathered (vote=True)
         self.cell = None if self.acquire else scrambling_init(mcc or 0, mnc or 0, colour_code or 0)
         self.cell_state = None   # [C] scrambling inits of the acquired cells (acquisition mode)
         # [C] bool: a CRC-good BSCH has been decoded on the channel.  Kept apart from cell_state,
@@ -167,6 +181,7 @@ class EtsiLowerMac:
         self._rows = None   # (soft rows [C, 2 stride], hard rows [C, stride], lead [C]): the carried tails
         self._alt = None    # link_quality: the other (soft rows, hard rows), which the next tails go to
         self._tdma = None   # [C] tetra_etsi_tdma: the carried timebases (mac=True)
+        self.cell_score = None   # vote=True: the cells start without incumbency (cell_state is kept)
 
     @property
     def cells(self):
@@ -209,10 +224,18 @@ class EtsiLowerMac:
                 self.acquired = np.zeros(C, bool)
             if self.acquired is None or len(self.acquired) != C:   # cell_state handed in from outside
                 self.acquired = np.zeros(C, bool)
-            c.check(c.lib.tetra_lmac_etsi_acquire(c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(nsym), C, smax,
-                                                  _hip.ptr(self.cell_state), _hip.ptr(nb), _hip.ptr(bursts),
-                                                  _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
-                    "tetra_lmac_etsi_acquire")
+            if self.vote:
+                ngood, agree = np.zeros(C, np.int32), np.zeros(C, np.int32)
+                c.check(c.lib.tetra_lmac_etsi_vote_groups(c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(nsym), C,
+                                                          smax, 1, self.vote_cap, _hip.ptr(self.cell_state),
+                                                          _hip.ptr(self._score(C)), _hip.ptr(ngood), _hip.ptr(agree),
+                                                          _hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks),
+                                                          _hip.ptr(t1)), "tetra_lmac_etsi_vote_groups")
+            else:
+                c.check(c.lib.tetra_lmac_etsi_acquire(c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(nsym), C, smax,
+                                                      _hip.ptr(self.cell_state), _hip.ptr(nb), _hip.ptr(bursts),
+                                                      _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
+                        "tetra_lmac_etsi_acquire")
             self.acquired |= acquired_channels(nk, blocks)
             used = self.cell_state
         else:
@@ -226,6 +249,12 @@ class EtsiLowerMac:
         lq = self._run_quality(c, soft, hard, 0, used, nb, bursts, nk, blocks, t1)
         return self._frames(C, nb, bursts, nk, blocks, t1, self._run_mac(c, C, nsym, nb, bursts, nk, blocks, t1, None),
                             lq)
+
+    def _score(self, C):
+        """cell_score for C channels (vote=True): zeros when new or of another length."""
+        if self.cell_score is None or len(self.cell_score) != C:
+            self.cell_score = np.zeros(C, np.int32)
+        return self.cell_score
 
     def _run_quality(self, c, soft, hard, origin, cells, nb, bursts, nk, blocks, t1):
         """tetra_etsi_link_quality on the rows the lower-MAC call read (link_quality=True; else None):
@@ -267,10 +296,17 @@ class EtsiLowerMac:
             ci = None
         srow, hrow, ns, stride, lead = stream[:5]
         nsrow, nhrow = stream[5:] if len(stream) > 5 else (srow, hrow)
-        c.check(c.lib.tetra_lmac_etsi_stream(c.handle, _hip.ptr(srow), _hip.ptr(hrow), _hip.ptr(ns), C, stride,
-                                             _hip.ptr(lead), _hip.ptr(nsrow), _hip.ptr(nhrow), ci, _hip.ptr(nb),
-                                             _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
-                "tetra_lmac_etsi_stream")
+        if self.vote and ci is not None:
+            c.check(c.lib.tetra_lmac_etsi_stream_vote(c.handle, _hip.ptr(srow), _hip.ptr(hrow), _hip.ptr(ns), C, stride,
+                                                      _hip.ptr(lead), _hip.ptr(nsrow), _hip.ptr(nhrow), self.vote_cap,
+                                                      ci, _hip.ptr(self._score(C)), None, _hip.ptr(nb),
+                                                      _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
+                    "tetra_lmac_etsi_stream_vote")
+        else:
+            c.check(c.lib.tetra_lmac_etsi_stream(c.handle, _hip.ptr(srow), _hip.ptr(hrow), _hip.ptr(ns), C, stride,
+                                                 _hip.ptr(lead), _hip.ptr(nsrow), _hip.ptr(nhrow), ci, _hip.ptr(nb),
+                                                 _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
+                    "tetra_lmac_etsi_stream")
         if ci is not None:
             self.acquired |= acquired_channels(nk, blocks)
             return self.cell_state

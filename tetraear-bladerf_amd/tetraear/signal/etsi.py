@@ -389,9 +389,15 @@ class BenchStep:
     dtype = "f32 (DSP), int8/int32 (Viterbi)"
 
     def __init__(self, c, C, N, fs, seed, device, snr_db=18.0, iq_format="cf32", demod="fused", cells="given",
-                 chunks=1):
+                 chunks=1, vote=False):
         import torch
         self.c, self.C, self.N, self.fs = c, C, N, fs
+        # vote (tools/probe_lmac_vote.py; the streaming step with cells="acquire" only): the cell by
+        # tetra_lmac_etsi_stream_vote, the scores in cell_score [C]
+        self.vote = bool(vote)
+        if self.vote and (cells != "acquire" or int(chunks) <= 1):
+            raise ValueError("vote=True chooses among acquired cells of a stream: cells='acquire', chunks > 1")
+        self.cell_score = torch.zeros(C, dtype=torch.int32, device=device) if self.vote else None
         # "acquire": the lower MAC finds each channel's cell in its BSCH (tetra_lmac_etsi_acquire,
         # per-channel state carried from step to step, as a receiver streaming chunks would);
         # "given": the synthesised cells are configured up front (tetra_etsi_set_cells)
@@ -630,6 +636,15 @@ class BenchStep:
                     self.lead.fill_(2 * RESERVE)
                 self._reset_lead = False
             acq = self.cells_mode == "acquire"
+            if self.vote:
+                c.check(c.lib.tetra_lmac_etsi_stream_vote(c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(nsym), self.C,
+                                                          self.stride, _hip.ptr(self.lead), _hip.ptr(nsoft),
+                                                          _hip.ptr(nhard), _hip.TETRA_ETSI_VOTE_CAP_DEFAULT,
+                                                          _hip.ptr(self.cell_state), _hip.ptr(self.cell_score), None,
+                                                          _hip.ptr(self.nburst), _hip.ptr(self.bursts),
+                                                          _hip.ptr(self.nblock), _hip.ptr(self.blocks),
+                                                          _hip.ptr(self.type1)), "lmac_etsi_stream_vote")
+                return
             c.check(c.lib.tetra_lmac_etsi_stream(c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(nsym), self.C,
                                                  self.stride, _hip.ptr(self.lead), _hip.ptr(nsoft), _hip.ptr(nhard),
                                                  _hip.ptr(self.cell_state) if acq else None, _hip.ptr(self.nburst),

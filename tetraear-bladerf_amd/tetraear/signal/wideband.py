@@ -247,22 +247,31 @@ class WidebandReceiver:
         totals them per carrier)."""
         return self._decode(x, np.asarray(cells, np.uint32), None, mac, timebase, tol, link_quality=link_quality)[0]
 
-    def decode_acquire(self, x, cell_init, mac=False, timebase=False, tol=64, link_quality=False):
+    def decode_acquire(self, x, cell_init, mac=False, timebase=False, tol=64, link_quality=False, score=None,
+                       vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT):
         """decode without given cells: cell_init [M] holds each carrier's scrambling init before the
         capture (3 = unknown); every carrier's cell comes from the last CRC-good BSCH over all of its
         chunk rows, and all of its rows are descrambled with it (tetra_lmac_etsi_acquire_groups, G =
         chunks per carrier).  Returns (frames as decode's, the inits after the capture [M] uint32,
         ngood [M] int32: the CRC-good BSCH blocks seen per carrier, copies in two chunks counted twice).
-        link_quality=True scores every carrier's blocks with the cell acquired for it."""
+        link_quality=True scores every carrier's blocks with the cell acquired for it.
+        score [M] int32 (C-contiguous, updated in place): the cell is chosen by the vote instead
+        (tetra_lmac_etsi_vote_groups: every CRC-good BSCH weighed by its soft bits, cell_init[k] defending
+        with score[k], scores bounded by vote_cap); at most 32 chunks per carrier.  The return is the same."""
         state = np.array(cell_init, np.uint32)
         if state.shape != (self.plan.M,):
             raise ValueError(f"cell_init holds {state.shape} inits, the receiver has {self.plan.M} carriers")
-        frames, ngood = self._decode(x, None, state, mac, timebase, tol, link_quality=link_quality)
+        if score is not None and not (isinstance(score, np.ndarray) and score.dtype == np.int32 and
+                                      score.shape == (self.plan.M,) and score.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"score must be a C-contiguous int32 array of {self.plan.M} (it is updated in place)")
+        frames, ngood = self._decode(x, None, state, mac, timebase, tol, link_quality=link_quality, score=score,
+                                     vote_cap=vote_cap)
         return frames, state, ngood
 
-    def _decode(self, x, cells, state, mac, timebase=False, tol=64, tdma=None, advance=0, link_quality=False):
-        """The chain behind decode (cells [M]) and decode_acquire (state [M], updated in place):
-        (frames, ngood or None).  timebase: tdma [M] ETSI_TDMA (in/out; None: new streams), whose bit0
+    def _decode(self, x, cells, state, mac, timebase=False, tol=64, tdma=None, advance=0, link_quality=False,
+                score=None, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT):
+        """The chain behind decode (cells [M]) and decode_acquire (state [M], updated in place; score [M]
+        int32 or None, likewise: the vote): (frames, ngood or None).  timebase: tdma [M] ETSI_TDMA (in/out; None: new streams), whose bit0
         moves on by ``advance`` bits after the call (WidebandStream)."""
         from tetraear.core.etsi import EtsiLowerMac, run_link_quality
         if timebase and (self.m2 % 2 or tol % 2 or tol < 0):
@@ -285,8 +294,15 @@ class WidebandReceiver:
             c.check(c.lib.tetra_lmac_etsi(c.handle, *rows, *outs), "tetra_lmac_etsi")
         else:
             ngood = np.zeros(M, np.int32)
-            c.check(c.lib.tetra_lmac_etsi_acquire_groups(c.handle, *rows, nchunk, _hip.ptr(state), _hip.ptr(ngood),
-                                                         *outs), "tetra_lmac_etsi_acquire_groups")
+            if score is not None:
+                agree = np.zeros(M, np.int32)
+                c.check(c.lib.tetra_lmac_etsi_vote_groups(c.handle, *rows, nchunk, int(vote_cap), _hip.ptr(state),
+                                                          _hip.ptr(score), _hip.ptr(ngood), _hip.ptr(agree), *outs),
+                        "tetra_lmac_etsi_vote_groups")
+            else:
+                c.check(c.lib.tetra_lmac_etsi_acquire_groups(c.handle, *rows, nchunk, _hip.ptr(state),
+                                                             _hip.ptr(ngood), *outs),
+                        "tetra_lmac_etsi_acquire_groups")
         pdus = None
         if timebase:   # merge and timebase per carrier on the device
             tdma = np.zeros(M, _hip.ETSI_TDMA) if tdma is None else tdma
@@ -350,6 +366,10 @@ class WidebandStream:
     carrier, carried from piece to piece in ``tdma`` [M] (reset() clears it): a buffer's carried tail
     is decoded again behind the anchor, which places those bursts without moving it.
     ``link_quality=True``: the frames and blocks carry the link-quality keys (WidebandReceiver.decode).
+    ``vote=True`` (acquisition only): a carrier's cell is chosen by the vote over each buffer's BSCH
+    blocks (WidebandReceiver.decode_acquire(score=...)), the score it gathers carried from piece to piece
+    in ``cell_score`` and read as ``cell_scores`` (reset() clears it).  A burst in the carried tail is
+    decoded again in the next buffer and votes again there, as it does in two overlapping chunks.
 
     The pieces may be [n, 2] int16 (SC16, a recording or the radio's buffer as it is): the tail is
     then kept in int16 and the buffer goes to the device in 4 B per sample.  If the pieces change
@@ -358,10 +378,13 @@ class WidebandStream:
     CARRY_Y = 2 * BURST_SAMPLES
 
     def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False, timebase=False,
-                 link_quality=False):
+                 link_quality=False, vote=False, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT):
         self.rx = WidebandReceiver(fs, M, m2, oversample)
         self.acquire, self.mac, self.timebase = cells is None, bool(mac), bool(timebase)
         self.link_quality = bool(link_quality)
+        self.vote, self.vote_cap = bool(vote), int(vote_cap)
+        if self.vote and not self.acquire:
+            raise ValueError("vote=True chooses among acquired cells: it takes no given cells")
         if self.timebase and m2 % 2:
             raise ValueError(f"timebase=True works in bits: m2 ({m2}) must be even")
         self._cells = None if self.acquire else np.ascontiguousarray(cells, np.uint32)
@@ -379,6 +402,11 @@ class WidebandStream:
         from tetraear.core.etsi import cell_of
         return [cell_of(v) if a else None for v, a in zip(self.cell_state, self.acquired)]
 
+    @property
+    def cell_scores(self):
+        """vote=True: the score each carrier's cell has gathered ([M] int32, a copy); else None."""
+        return None if self.cell_score is None else self.cell_score.copy()
+
     def reset(self):
         self.tail = np.zeros(0, np.complex64)
         self.y0 = 0                                    # stream position of the buffer's first output
@@ -387,6 +415,7 @@ class WidebandStream:
         # decoded on it (an all-zero cell has the init of "unknown")
         self.cell_state = np.full(self.M, 3, np.uint32) if self.acquire else None
         self.acquired = np.zeros(self.M, bool) if self.acquire else None
+        self.cell_score = np.zeros(self.M, np.int32) if self.vote else None   # the vote's score per carrier
         # timebase: each carrier's tetra_etsi_tdma; bit0 = the stream bit of the buffer's first output
         self.tdma = np.zeros(self.M, _hip.ETSI_TDMA) if self.timebase else None
 
@@ -394,7 +423,8 @@ class WidebandStream:
         if self.timebase:
             state = np.array(self.cell_state, np.uint32) if self.acquire else None
             frames, ngood = self.rx._decode(buf, self._cells, state, True, True, 64, self.tdma, advance,
-                                            link_quality=self.link_quality)
+                                            link_quality=self.link_quality, score=self.cell_score,
+                                            vote_cap=self.vote_cap)
             if self.acquire:
                 self.cell_state = state
                 self.acquired |= ngood > 0
@@ -404,6 +434,8 @@ class WidebandStream:
             kw["link_quality"] = True
         if not self.acquire:
             return self.rx.decode(buf, self._cells, **kw)
+        if self.vote:
+            kw.update(score=self.cell_score, vote_cap=self.vote_cap)
         frames, self.cell_state, ngood = self.rx.decode_acquire(buf, self.cell_state, **kw)
         self.acquired |= ngood > 0
         return frames
@@ -474,7 +506,8 @@ class BenchStep:
     chunk), lower MAC (sync, Viterbi, CRC) on all of them.  TETRA_WB_CELLS=acquire (default
     "given": every carrier's synthesised cell is configured): the lower MAC acquires each carrier's
     cell itself over all of its chunks (tetra_lmac_etsi_acquire_groups), the M inits kept on the
-    device from step to step with the context that runs the lower MAC.  TETRA_WB_MAC=timebase: the
+    device from step to step with the context that runs the lower MAC; TETRA_WB_CELLS=vote: the same
+    by tetra_lmac_etsi_vote_groups, the scores in cell_score [M].  TETRA_WB_MAC=timebase: the
     capture is synthesised on the slot grid and tetra_etsi_mac_groups follows the lower MAC on the same
     context (PDU headers, the merge of each carrier's chunk rows, one TDMA timebase per carrier resident
     on the device; every step decodes the same capture, so bit0 does not advance).  TETRA_WB_IQ=sc16
@@ -534,11 +567,15 @@ class BenchStep:
         # every chunk of carrier k uses carrier k's scrambling code
         self.cells = cells.repeat_interleave(self.nchunk).contiguous()
         mode = os.environ.get("TETRA_WB_CELLS", "given")
-        if mode not in ("given", "acquire"):
-            raise ValueError(f"TETRA_WB_CELLS={mode!r}: given or acquire")
-        self.acquire = mode == "acquire"
+        if mode not in ("given", "acquire", "vote"):
+            raise ValueError(f"TETRA_WB_CELLS={mode!r}: given, acquire or vote")
+        self.acquire = mode in ("acquire", "vote")
+        self.vote = mode == "vote"   # acquisition by tetra_lmac_etsi_vote_groups, the scores in cell_score [M]
+        if self.vote:
+            self.cell_score = torch.zeros(M, dtype=torch.int32, device=device)
+            self.agree = torch.zeros(M, dtype=torch.int32, device=device)
         if self.acquire:   # the acquisition state: one init per carrier (3 = unknown), CRC-good BSCH counts
-            self.cells_mode = "acquire"
+            self.cells_mode = mode
             self.cells_true = cells
             self.cell_state = torch.full((M,), 3, dtype=torch.int32, device=device)
             self.ngood = torch.zeros(M, dtype=torch.int32, device=device)
@@ -665,6 +702,15 @@ class BenchStep:
             self._mac(c)
 
     def _lmac_rows(self, c):
+        if self.acquire and self.vote:
+            c.check(c.lib.tetra_lmac_etsi_vote_groups(c.handle, _hip.ptr(self.soft), _hip.ptr(self.hard),
+                                                      _hip.ptr(self.nsym), self.C, self.sm, self.nchunk,
+                                                      _hip.TETRA_ETSI_VOTE_CAP_DEFAULT, _hip.ptr(self.cell_state),
+                                                      _hip.ptr(self.cell_score), _hip.ptr(self.ngood),
+                                                      _hip.ptr(self.agree), _hip.ptr(self.nburst), _hip.ptr(self.bursts),
+                                                      _hip.ptr(self.nblock), _hip.ptr(self.blocks),
+                                                      _hip.ptr(self.type1)), "lmac_etsi_vote_groups")
+            return
         if self.acquire:
             c.check(c.lib.tetra_lmac_etsi_acquire_groups(c.handle, _hip.ptr(self.soft), _hip.ptr(self.hard),
                                                          _hip.ptr(self.nsym), self.C, self.sm, self.nchunk,
