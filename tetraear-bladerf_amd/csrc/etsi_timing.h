@@ -257,8 +257,10 @@ __device__ __forceinline__ float om_all(const float2 *y, int M2, int lane) {
 // (|delta| <= 1.5, the cubic window), the ring holds [0, 320) before the loop, and block b first writes
 // the 256 samples the previous block loaded into registers, [320 + 256 (b - 1), 320 + 256 b) (over
 // [256 b - 448, 256 b - 192), which no later block reads), then loads the next 256: each block's window
-// reads wait on LDS, not on L2 / HBM.  Same interpolation arithmetic, same bits.  RING = 2 keeps two
-// blocks' loads in flight in registers (pre, pre2: the ring's contents at every block are the same).
+// reads wait on LDS, not on L2 / HBM.  (A continued stream's first symbol can lie further into y: all of
+// these indices are then counted from the ring's origin `org`, see below.)  Same interpolation
+// arithmetic, same bits.  RING = 2 keeps two blocks' loads in flight in registers (pre, pre2: the
+// ring's contents at every block are the same).
 // LEAN (k_timing): the Oerder-Meyr pass by om_all (all quarters' loads together) instead of om_part per
 // quarter, and no d_j stores -- the decision pass recomputes d_j from the stored symbols (timing_decide_sym).
 // OMC (k_timing's OMG form): the Oerder-Meyr class sums are given (omc = A0..A3, wave-uniform) --
@@ -344,20 +346,28 @@ __device__ __forceinline__ TrackOut timing_track(const float2 *y, int M2, float 
             return n < M2 ? y[n] : make_float2(0.f, 0.f);
         }
     };
+    // RING, streaming: the first symbol is at base = the carried base + yoff, and yoff goes up to
+    // TETRA_ETSI_MARGIN + the outputs of one window period (2 up: 151 at 127 kSps), past what a ring
+    // filled from y[0] holds for block 0.  The ring starts at org instead, a multiple of 4 with
+    // base - org in [8, 12) (0 while base < 8, and without a carried loop, where base < 4): block b
+    // then reads y[org + 256 b + 3, org + 256 b + 268), inside the [org + 256 b - 192, org + 256 b + 320)
+    // the ring holds.
+    int org = 0;
     if constexpr (RING > 0) {
+        if (ti.acq) org = max(0, (int)base - 8) & ~3;
 #pragma unroll
-        for (int u = 0; u < 5; ++u) ring[64 * u + lane] = ld(64 * u + lane);
+        for (int u = 0; u < 5; ++u) ring[(org + 64 * u + lane) & (TRING - 1)] = ld(org + 64 * u + lane);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) pre[u] = ld(320 + 64 * u + lane);
+        for (int u = 0; u < 4; ++u) pre[u] = ld(org + 320 + 64 * u + lane);
         if constexpr (RING > 1) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) pre2[u] = ld(576 + 64 * u + lane);
+            for (int u = 0; u < 4; ++u) pre2[u] = ld(org + 576 + 64 * u + lane);
         }
     }
     for (int kb = kstart;; kb += 64) {
         if constexpr (RING > 0) {
             if (kb != kstart) {   // the previous block's loads: y[320 + 256 (b - 1) ...)
-                const int n0 = 320 + 4 * (kb - kstart) - 256;
+                const int n0 = org + 320 + 4 * (kb - kstart) - 256;
 #pragma unroll
                 for (int u = 0; u < 4; ++u) ring[(n0 + 64 * u + lane) & (TRING - 1)] = pre[u];
                 if constexpr (RING > 1) {

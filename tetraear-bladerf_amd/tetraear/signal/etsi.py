@@ -116,6 +116,24 @@ def stream_window(plan, x_total, y_done, n):
     return tuple(x.value for x in v)
 
 
+def stream_history(plan):
+    """Input samples before the chunk that a streaming window can re-read: an upper bound of
+    x_total - s over every chunk sequence (tetra_etsi_stream_window), from the window arithmetic.
+
+    With y_done = M2(x_total) outputs done, the window starts at s = per * floor((y_done - MARGIN) /
+    ups), per = q1 down (doubled when odd) input samples carrying ups outputs.  From
+    q1 M1 >= x_total - L1 + 1, down y_done >= up M1 - Lp + 1 and floor(a / ups) >= (a - ups + 1) / ups:
+
+        x_total - s <= per + q1 ((Lp - 1) + down (MARGIN - 1)) / up + L1 - 1
+
+    one (possibly doubled) period, the stage-2 span and the margin in input samples, and stage 1's
+    taps.  2.4 MSps: 1447; the largest among the integer-kHz rates, 4.953 MSps: 6046."""
+    q1, L1, up, down, Lp = plan.q1, plan.L1, plan.up, plan.down, plan.Lp
+    pb = q1 * down
+    per = 2 * pb if pb % 2 else pb
+    return per + -(-q1 * ((Lp - 1) + down * (MARGIN - 1)) // up) + L1 - 1
+
+
 def _sc16_to_cf32(x):
     """[C, N, 2] int16 -> [C, N] complex64 scaled 1/32768 (capture.py:241-269; exact)."""
     return ((x[..., 0].astype(np.float32) + 1j * x[..., 1].astype(np.float32)) / np.float32(32768)).astype(
@@ -128,8 +146,8 @@ class EtsiStream:
     continuous_capture.py:20) demodulated as ONE symbol stream per channel.
 
     Each chunk's channel filter runs over a window that starts before the chunk -- the previous
-    chunks' last samples are kept here (``HIST``) -- at a multiple of q1 * down input samples, so its
-    polyphase phases are those of a run over the whole capture (tetra_etsi_stream_window); the timing
+    chunks' last samples are kept here (``hist_len`` of them: stream_history) -- at a multiple of
+    q1 * down input samples, so its polyphase phases are those of a run over the whole capture (tetra_etsi_stream_window); the timing
     loop of every channel is carried in ``track`` (tetra_etsi_track: base, delta, last symbol); the
     AFC mixer (``freq_offsets``) runs on the window with the capture's global sample index, so its
     phase is continuous too.  Row c of the outputs holds the carried last symbol of the previous
@@ -137,11 +155,12 @@ class EtsiStream:
     the seam -- exactly the row layout demod_batch returns, ready for EtsiLowerMac.decode_stream.
     oracle/etsi.py Stream restates it."""
 
-    HIST = 4096   # input samples kept per channel (a window re-reads < 1600 at every supported rate)
-
     def __init__(self, sample_rate=2.4e6, channels=1):
         self.sample_rate = sample_rate
         self.plan = etsi_plan(sample_rate)
+        # input samples kept per channel: what a window of this plan can re-read (1447 at 2.4 MSps, up
+        # to 6046 at the rates rate_design serves)
+        self.hist_len = stream_history(self.plan)
         self.C = int(channels)
         self.reset()
 
@@ -209,7 +228,7 @@ class EtsiStream:
         c.check(c.lib.tetra_demod_etsi_stream(c.handle, self.plan, _hip.ptr(dwin), fmt, self.C, dwin.shape[1], W, int(yoff),
                                               _hip.ptr(self.track), _hip.ptr(sym), _hip.ptr(soft), _hip.ptr(hard),
                                               _hip.ptr(ns), smax, smax, _hip.ptr(diag)), "tetra_demod_etsi_stream")
-        keep = min(self.HIST, win.shape[1])
+        keep = min(self.hist_len, win.shape[1])
         self.hist = np.ascontiguousarray(win[:, win.shape[1] - keep:])
         self.x_total += n
         self.y_done = y_next
@@ -470,8 +489,10 @@ class BenchStep:
         self.kchunk = 0
         if self.stream:
             # output rows: TETRA_ETSI_RESERVE dibits for the carried tail, then a window's symbols
-            # (a window is the chunk + < 1600 samples of the previous one)
-            _, self.M2, sm1 = lengths(self.plan, N + 4096)
+            # (a window is the chunk + at most stream_history samples of the previous ones: 1447 at
+            # 2.4 MSps, up to 6046; never fewer than the 4096 the rows always allowed for, so the row
+            # layout of a rate that fitted them stays what it was)
+            _, self.M2, sm1 = lengths(self.plan, N + max(4096, stream_history(self.plan)))
             self.smax = sm1 + 1
             self.stride = RESERVE + self.smax
             self.track = torch.zeros((C, TRACK.itemsize // 4), dtype=torch.int32, device=device)
