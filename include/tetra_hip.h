@@ -700,6 +700,70 @@ int tetra_etsi_link_quality(tetra_ctx *ctx, const int8_t *softbits, const uint8_
                             const int32_t *blocks, const uint8_t *type1,
                             int32_t *bq /*[C][MAXB][4]*/, int32_t *kq /*[C][MAXJ][4]*/);
 
+/* ---------------------------------------------------------------- timebase vote (a new symbol of ABI
+ * version 2; nothing existing changed shape).  tetra_etsi_mac_groups takes every STATUS 0 SYNC at its
+ * word: one false CRC pass on a BSCH (2^-16 per failed block, its TN / FN / MN valid about half the
+ * time) or a neighbour cell's synchronisation burst re-anchors the carrier's slot grid, and it keeps
+ * the copy of a burst in the earlier row whatever that copy decoded.  tetra_etsi_mac_vote_groups is that
+ * call with the timebase chosen by a vote and keep chosen by quality, from the records of
+ * tetra_etsi_link_quality for the same rows and the same lower-MAC outputs (bq, kq).  npdu and pdus are
+ * tetra_etsi_mac's.
+ *
+ * The rule (exact integers, positions int64).
+ *   Order.  A group's live bursts (row i, b < nburst clamped to 0..MAXB) have pos = i row_bits + start
+ *     bit and are taken in the order (pos, row, b), as in tetra_etsi_mac_groups.
+ *   Clusters.  A cluster is a maximal run of that order in which every burst's pos exceeds the previous
+ *     burst's by at most tol_bits (the chain rule); its first burst is what tetra_etsi_mac_groups keeps.
+ *   Keep.  Burst (c, b) has a quality key Q.  good = the number of j < nblock[c] (clamped to 0..MAXJ)
+ *     with blocks[c][j] naming burst b, a kind in 0..2 and crc_ok != 0.  bq[c][b][TERR] < 0 (an invalid
+ *     burst): Q = -1.  Else Q = good << 32 | (60 - min(60, TERR + HERR)) << 16 | min(WSUM, 65535), with
+ *     TERR, HERR, WSUM from bq (a negative sum or WSUM, which no record has, reads as 0).  In every
+ *     cluster exactly one burst has keep = 1: the one with the largest Q, on a tie the first in the order.
+ *   Ballots.  A burst has an own SYNC as in tetra_etsi_mac_groups: an SB whose BSCH block is CRC-good
+ *     with a STATUS 0 record, of slot count s.  Its weight is w = max(1, WSUM - 2 WERR) from that block's
+ *     kq record -- the cell vote's w, at most 15240 (a larger value, which no record has, reads as
+ *     15240); a kq record whose NERR reads -1 gives w = 1.  In every cluster the own-SYNC burst with the
+ *     largest w (on a tie the first) is the cluster's ballot, cast where the walk reaches it; every other
+ *     burst of the cluster is walked as a burst without a SYNC: one burst on air casts one ballot.
+ *   The walk.  One per group over all live bursts in the order, kept or not, p = bit0 + pos.  State:
+ *     tdma[g] and score = max(0, tscore[g]).  Rule 1 of tetra_etsi_mac_groups gives (pred, k); a lock
+ *     that expires (k >= TETRA_TDMA_EXPIRE) also sets score to 0.  For a ballot (s, w):
+ *       a. not locked: anchor = (p, s), locked, score = min(cap, w); the row is s, FLAGS 1; BALLOTS++;
+ *       b. locked and pred == s: score = min(cap, score + w), anchor = (p, s); the row is s, FLAGS 1;
+ *          BALLOTS++, AGREED++;
+ *       c. locked and pred != s (another slot, or none): if w > score the ballot wins: anchor = (p, s),
+ *          score = min(cap, w - score); the row is s, FLAGS 1 | 2; BALLOTS++, WON++.  Otherwise score -=
+ *          w; if pred is a slot the burst takes it with FLAGS 2 | 4 (bit 2: own SYNC outvoted) and the
+ *          anchor moves to (p, pred) only if k >= 1; if pred is none the row reads 0, 0, 0, 0;
+ *          BALLOTS++, OUTVOTED++.
+ *     Every other burst follows rules 3 and 4 of tetra_etsi_mac_groups.  After the walk bit0 += advance
+ *     and tscore[g] = score; without a ballot tscore changes only by expiry (and a negative one to 0).
+ * tvote [C / G][TETRA_TV_FIELDS] (fully written): the group's ballots of this call and how they fared.
+ *
+ * On an input where no cluster holds two own-SYNC bursts and tetra_etsi_mac_groups sets FLAGS bit 1
+ * nowhere, slots and tdma equal tetra_etsi_mac_groups's from any incoming score, and keep equals it
+ * wherever a cluster's copies have equal Q.  (An SB that arrives as the lock expires reads FLAGS 1 here,
+ * case a, and FLAGS 3 there.)  Why a cap this small is safe: a stream that really restarted on another
+ * bit alignment places no burst on the old grid, so the lock expires by itself after TETRA_TDMA_EXPIRE
+ * slots and the next SYNC starts from score 0; the cap only bounds how long a grid that happens to share
+ * the alignment defends its slot numbers.  TETRA_TDMA_VOTE_CAP_DEFAULT: four full-scale BSCH blocks, a
+ * stated choice, not a measurement.
+ *
+ * TETRA_E_INVALID with nothing written: what tetra_etsi_mac_groups refuses, a NULL array, cap <= 0.
+ * Host or device pointers; with device pointers the call enqueues two kernels on the context stream and
+ * returns without waiting (no allocation, no synchronising copy).  struct tetra_etsi_tdma is unchanged:
+ * the score lives in its own array. */
+#define TETRA_TDMA_VOTE_CAP_DEFAULT 60960
+enum { TETRA_TV_BALLOTS = 0, TETRA_TV_AGREED, TETRA_TV_OUTVOTED, TETRA_TV_WON, TETRA_TV_FIELDS = 4 };
+int tetra_etsi_mac_vote_groups(tetra_ctx *ctx, const int32_t *nsym, size_t C, size_t G, int64_t row_bits,
+                               int64_t tol_bits, int64_t advance, int32_t cap,
+                               const int32_t *nburst, const int32_t *bursts, const int32_t *nblock,
+                               const int32_t *blocks, const uint8_t *type1,
+                               const int32_t *bq /*[C][MAXB][4] in*/, const int32_t *kq /*[C][MAXJ][4] in*/,
+                               tetra_etsi_tdma *tdma /*[C/G] in/out*/, int32_t *tscore /*[C/G] in/out*/,
+                               int32_t *keep, int32_t *slots, int32_t *npdu, int32_t *pdus,
+                               int32_t *tvote /*[C/G][TETRA_TV_FIELDS] out*/);
+
 /* The ETSI receiver's AFC mixer on a streaming window: out [C][N] cf32 = iq (cf32 rows ld samples
  * apart) x exp(-j 2 pi f (n0 + n) / fs), n0 = the window's first sample in the capture (frequency_shift's
  * float64 arithmetic, processor.py:85-100, with one continuous phase across windows); mix_c [C] as

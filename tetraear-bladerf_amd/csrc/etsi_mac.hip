@@ -10,7 +10,7 @@
 //               block walk, then per group of overlapping rows -- a wideband carrier's chunks -- one
 //               wave that rank-sorts the group's bursts by position in LDS, keeps each burst once and
 //               runs one timebase over the merged order.
-#include "common.h"
+#include "etsi_mac.h"
 
 namespace {
 
@@ -410,6 +410,12 @@ __global__ __launch_bounds__(64) void k_tdma_groups(int G, int64_t row_bits, int
 }
 
 }  // namespace
+
+void launch_mac_walk(tetra_ctx *ctx, size_t C, const int32_t *nburst, const int32_t *bursts, const int32_t *nblock,
+                     const int32_t *blocks, const uint8_t *type1, int32_t *own, int32_t *npdu, int32_t *pdus) {
+    hipLaunchKernelGGL(k_mac_walk, dim3(grid_for(C * MAC_LANES, MAC_BLOCK)), dim3(MAC_BLOCK), 0, ctx->stream, (int)C,
+                       nburst, bursts, nblock, blocks, type1, own, npdu, pdus);
+}
 
 extern "C" int tetra_etsi_mac(tetra_ctx *ctx, const int32_t *nsym, size_t C, const int32_t *nburst,
                               const int32_t *bursts, const int32_t *nblock, const int32_t *blocks,

@@ -85,6 +85,10 @@ BQ_TERR, BQ_HERR, BQ_WSUM, BQ_NSAT = range(4)
 # the cell vote (tetra_lmac_etsi_vote_groups / _stream_vote): the default bound on a cell's score, eight
 # full-scale BSCH blocks (120 x 127 each)
 TETRA_ETSI_VOTE_CAP_DEFAULT = 8 * 120 * 127
+# the timebase vote (tetra_etsi_mac_vote_groups): the default bound on a timebase's score, four full-scale
+# BSCH blocks; the tvote record; FLAGS bit 2 of a slot row, "own SYNC outvoted"
+TETRA_TDMA_VOTE_CAP_DEFAULT = 4 * 120 * 127
+TV_BALLOTS, TV_AGREED, TV_OUTVOTED, TV_WON, TV_FIELDS = range(5)
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -160,6 +164,9 @@ def _bind(L):
         "tetra_etsi_mac": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
         "tetra_etsi_mac_groups": (_i32, [_vp, _vp, _sz, _sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "tetra_etsi_mac_vote_groups": (_i32, [_vp, _vp, _sz, _sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp]),
         "tetra_etsi_link_quality": (_i32, [_vp, _vp, _vp, _sz, _sz, ctypes.c_int32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp]),
         "tetra_etsi_mix": (_i32, [_vp, _vp, _sz, _sz, _sz, _vp, ctypes.c_double, ctypes.c_int64, _vp]),

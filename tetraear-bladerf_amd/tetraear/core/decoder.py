@@ -89,7 +89,7 @@ class TetraDecoder:
     """Decodes TETRA frames from demodulated symbols (decoder.py:16)."""
 
     def __init__(self, key_manager=None, auto_decrypt: bool = True, mode=None, mac: bool = False,
-                 link_quality: bool = False, vote: bool = False):
+                 link_quality: bool = False, vote: bool = False, timebase_vote: bool = False):
         self.SYNC_PATTERN = [0, 1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0,
                              1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0]
         self.FRAME_LENGTH = 510
@@ -104,6 +104,8 @@ class TetraDecoder:
         self.etsi_mac = bool(mac)   # mode="etsi": TDMA timebase + MAC PDU headers on the frames (EtsiLowerMac(mac=True))
         self.etsi_link_quality = bool(link_quality)   # mode="etsi": burst and block quality figures on the frames
         self.etsi_vote = bool(vote)   # mode="etsi": the cell by the soft-weighted vote (EtsiLowerMac(vote=True))
+        # mode="etsi", mac=True: the timebase by the vote on SYNC bursts (EtsiLowerMac(timebase_vote=True))
+        self.etsi_timebase_vote = bool(timebase_vote)
 
     # ------------------------------------------------------------------ keys and the reference's rest
     def set_keys(self, keys):
@@ -420,5 +422,6 @@ class TetraDecoder:
     def _etsi_rx(self):
         if self._etsi is None:
             from tetraear.core.etsi import EtsiLowerMac
-            self._etsi = EtsiLowerMac(mac=self.etsi_mac, link_quality=self.etsi_link_quality, vote=self.etsi_vote)
+            self._etsi = EtsiLowerMac(mac=self.etsi_mac, link_quality=self.etsi_link_quality, vote=self.etsi_vote,
+                                      timebase_vote=self.etsi_timebase_vote)
         return self._etsi

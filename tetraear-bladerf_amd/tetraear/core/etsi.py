@@ -156,12 +156,28 @@ class EtsiLowerMac:
     correlation of its soft bits with its re-encoded codeword, and the cell kept so far defends with
     ``cell_score`` [C] (int32, kept next to ``cell_state``; reset_stream() clears it), bounded by
     ``vote_cap``.  One false CRC pass or a neighbour cell's burst then no longer replaces an established
-    cell.  With one cell per channel the frames are those of ``vote=False``."""
+    cell.  With one cell per channel the frames are those of ``vote=False``.
+
+    ``timebase_vote=True`` (with ``mac=True``): the timebase comes from tetra_etsi_mac_vote_groups (G = 1,
+    row_bits = 0, advance = 2 max(nsym - 1, 0)) instead of tetra_etsi_mac: a SYNC moves the channel's slot
+    grid only if its soft-bit weight outvotes the score the grid has gathered, kept in ``tdma_score`` [C]
+    beside the timebases (reset_stream() clears both) and bounded by ``tdma_cap``; ``slot_flags`` bit 2
+    marks a burst whose own SYNC was outvoted.  tetra_etsi_link_quality runs first for the weights (the
+    streaming origin for streaming rows; its keys reach the frames only with ``link_quality=True``).  The
+    one difference from tetra_etsi_mac on a stream without contradictions: a burst behind the anchor does
+    not drop the lock (tetra_etsi_mac_groups' rule 1)."""
 
     def __init__(self, mcc=None, mnc=None, colour_code=None, mac=False, link_quality=False, vote=False,
-                 vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT):
+                 vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, timebase_vote=False,
+                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT):
         self.mac = bool(mac)
         self.link_quality = bool(link_quality)
+        self.timebase_vote, self.tdma_cap = bool(timebase_vote), int(tdma_cap)
+        if self.timebase_vote and not self.mac:
+            raise ValueError("timebase_vote=True chooses the timebase of mac=True")
+        if self.timebase_vote and self.tdma_cap <= 0:
+            raise ValueError(f"tdma_cap ({tdma_cap}) must be positive")
+        self.tdma_votes = None   # [C, 4] int32: the last call's ballots (cast, agreed, outvoted, won)
         self.acquire = mcc is None and mnc is None and colour_code is None
         self.vote, self.vote_cap = bool(vote), int(vote_cap)
         if self.vote and not self.acquire:
@@ -181,6 +197,7 @@ class EtsiLowerMac:
         self._rows = None   # (soft rows [C, 2 stride], hard rows [C, stride], lead [C]): the carried tails
         self._alt = None    # link_quality: the other (soft rows, hard rows), which the next tails go to
         self._tdma = None   # [C] tetra_etsi_tdma: the carried timebases (mac=True)
+        self.tdma_score = None   # [C] int32: the score each timebase has gathered (timebase_vote=True)
         self.cell_score = None   # vote=True: the cells start without incumbency (cell_state is kept)
 
     @property
@@ -247,8 +264,9 @@ class EtsiLowerMac:
                     "tetra_lmac_etsi")
             used = cells
         lq = self._run_quality(c, soft, hard, 0, used, nb, bursts, nk, blocks, t1)
-        return self._frames(C, nb, bursts, nk, blocks, t1, self._run_mac(c, C, nsym, nb, bursts, nk, blocks, t1, None),
-                            lq)
+        return self._frames(C, nb, bursts, nk, blocks, t1,
+                            self._run_mac(c, C, nsym, nb, bursts, nk, blocks, t1, None, lq),
+                            lq if self.link_quality else None)
 
     def _score(self, C):
         """cell_score for C channels (vote=True): zeros when new or of another length."""
@@ -257,15 +275,16 @@ class EtsiLowerMac:
         return self.cell_score
 
     def _run_quality(self, c, soft, hard, origin, cells, nb, bursts, nk, blocks, t1):
-        """tetra_etsi_link_quality on the rows the lower-MAC call read (link_quality=True; else None):
-        (bq, kq).  cells [C]: the inits the rows were descrambled with."""
-        if not self.link_quality:
+        """tetra_etsi_link_quality on the rows the lower-MAC call read (link_quality=True or
+        timebase_vote=True; else None): (bq, kq).  cells [C]: the inits the rows were descrambled with."""
+        if not (self.link_quality or self.timebase_vote):
             return None
         return run_link_quality(c, soft, hard, origin, 1, cells, nb, bursts, nk, blocks, t1)
 
-    def _run_mac(self, c, C, nsym, nb, bursts, nk, blocks, t1, tdma):
+    def _run_mac(self, c, C, nsym, nb, bursts, nk, blocks, t1, tdma, lq=None, score=None):
         """tetra_etsi_mac on the lower MAC's outputs (mac=True; else None): (slots, npdu, pdus).
-        tdma None: a new stream per channel."""
+        tdma None: a new stream per channel.  timebase_vote=True: tetra_etsi_mac_vote_groups with the
+        call's link-quality records lq and the scores score [C] (None: zeros) instead."""
         if not self.mac:
             return None
         if tdma is None:
@@ -273,6 +292,24 @@ class EtsiLowerMac:
         slots = np.zeros((C, _hip.ETSI_MAXB, _hip.SLOT_FIELDS), np.int32)
         npdu = np.zeros((C, _hip.ETSI_MAXJ), np.int32)
         pdus = np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.PDU_FIELDS), np.int32)
+        if self.timebase_vote:
+            score = np.zeros(C, np.int32) if score is None else score
+            self.tdma_votes = np.zeros((C, _hip.TV_FIELDS), np.int32)
+            keep = np.zeros((C, _hip.ETSI_MAXB), np.int32)   # one row a group: a row's bursts are a slot apart
+            for n in np.unique(nsym):   # advance is one value a call: the channels of one chunk length together
+                idx = np.flatnonzero(nsym == n)
+                every = len(idx) == C
+                a = [v if every else np.ascontiguousarray(v[idx])
+                     for v in (nsym, nb, bursts, nk, blocks, t1, lq[0], lq[1], tdma, score, keep, slots, npdu, pdus,
+                               self.tdma_votes)]
+                c.check(c.lib.tetra_etsi_mac_vote_groups(c.handle, _hip.ptr(a[0]), len(idx), 1, 0, 32,
+                                                         2 * max(int(n) - 1, 0), self.tdma_cap,
+                                                         *[_hip.ptr(v) for v in a[1:]]), "tetra_etsi_mac_vote_groups")
+                if not every:
+                    for dst, src in zip((tdma, score, slots, npdu, pdus, self.tdma_votes),
+                                        (a[8], a[9], a[11], a[12], a[13], a[14])):
+                        dst[idx] = src
+            return slots, npdu, pdus
         c.check(c.lib.tetra_etsi_mac(c.handle, _hip.ptr(nsym), C, _hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk),
                                      _hip.ptr(blocks), _hip.ptr(t1), _hip.ptr(tdma), _hip.ptr(slots), _hip.ptr(npdu),
                                      _hip.ptr(pdus)), "tetra_etsi_mac")
@@ -335,7 +372,8 @@ class EtsiLowerMac:
             self._alt = None
         srow, hrow, lead = self._rows
         stride = hrow.shape[1]
-        if self.link_quality and self._alt is None:
+        intact = self.link_quality or self.timebase_vote   # the quality pass reads the rows after the call
+        if intact and self._alt is None:
             self._alt = (np.zeros_like(srow), np.zeros_like(hrow))
         hrow[:, R:R + smax] = hard
         srow[:, 2 * R:2 * R + 2 * smax] = soft
@@ -345,16 +383,20 @@ class EtsiLowerMac:
         blocks = np.zeros((C, _hip.ETSI_MAXJ, 4), np.int32)
         t1 = np.zeros((C, _hip.ETSI_MAXJ, 268), np.uint8)
         # link_quality: the tails go to the other rows, these stay as the call read them
-        nxt = self._alt if self.link_quality else ()
+        nxt = self._alt if intact else ()
         used = self._run_stream(_hip.ctx(), C, nb, bursts, nk, blocks, t1, cells,
                                 (srow, hrow, nsym, stride, lead) + tuple(nxt))
         lq = self._run_quality(_hip.ctx(), srow, hrow, 2 * R, used, nb, bursts, nk, blocks, t1)
-        if self.link_quality:
+        if intact:
             self._rows, self._alt = (nxt[0], nxt[1], lead), (srow, hrow)
         if self.mac and (self._tdma is None or len(self._tdma) != C):
             self._tdma = np.zeros(C, _hip.ETSI_TDMA)
+            self.tdma_score = None
+        if self.timebase_vote and self.tdma_score is None:
+            self.tdma_score = np.zeros(C, np.int32)
         return self._frames(C, nb, bursts, nk, blocks, t1,
-                            self._run_mac(_hip.ctx(), C, nsym, nb, bursts, nk, blocks, t1, self._tdma), lq)
+                            self._run_mac(_hip.ctx(), C, nsym, nb, bursts, nk, blocks, t1, self._tdma, lq,
+                                          self.tdma_score), lq if self.link_quality else None)
 
     @staticmethod
     def _frames(C, nb, bursts, nk, blocks, t1, mac=None, lq=None):

@@ -169,6 +169,7 @@ class WidebandReceiver:
         self.plan = wb_plan(fs, M, oversample)
         self.etsi = etsi_plan(2.4e6)   # timing-loop constants (the channel-filter taps are not used)
         self.m2 = m2
+        self.tvote = None   # [M, 4] int32: the ballots of the last decode with timebase="vote"
 
     def channelize(self, x, n_keep=None):
         """x [Nw] complex64 or [Nw, 2] int16 -> y [M][n_keep] complex64 at 72 kHz."""
@@ -230,7 +231,8 @@ class WidebandReceiver:
                 ns.reshape(M, ck.nchunk))
 
 
-    def decode(self, x, cells, mac=False, timebase=False, tol=64, link_quality=False):
+    def decode(self, x, cells, mac=False, timebase=False, tol=64, link_quality=False,
+               tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT):
         """x [Nw] -> per carrier the frames decoded from it, each burst once (merge_chunks), in row
         order: demod, then the ETSI lower MAC on every (carrier, chunk) with carrier k's scrambling
         init cells[k].  A frame is the lower MAC's dict (core/etsi.py) plus "chunk" and "sample" (its
@@ -244,11 +246,19 @@ class WidebandReceiver:
         needs it and m2 even (the device works in bits), else ValueError.  link_quality=True: the
         frames and blocks gain EtsiLowerMac(link_quality=True)'s keys, from one tetra_etsi_link_quality
         call over all (carrier, chunk) rows with G = chunks per carrier (core/etsi.py carrier_quality
-        totals them per carrier)."""
-        return self._decode(x, np.asarray(cells, np.uint32), None, mac, timebase, tol, link_quality=link_quality)[0]
+        totals them per carrier).  timebase="vote": as timebase=True by tetra_etsi_mac_vote_groups -- a
+        SYNC moves a carrier's slot grid only if its soft-bit weight outvotes the score the grid has
+        gathered (bounded by tdma_cap), a burst that two chunks share casts one ballot, and of its copies
+        the one that decoded best is kept (most CRC-good blocks, then fewest known-bit errors, then the
+        strongest soft bits) instead of the earlier row's.  tetra_etsi_link_quality runs first, on the
+        intact rows, for the weights; its keys appear on the frames only with link_quality=True.
+        ``slot_flags`` bit 2: the burst's own SYNC was outvoted.  ``tvote`` [M, 4] holds the last call's
+        ballots per carrier (cast, agreed, outvoted, won)."""
+        return self._decode(x, np.asarray(cells, np.uint32), None, mac, timebase, tol, link_quality=link_quality,
+                            tdma_cap=tdma_cap)[0]
 
     def decode_acquire(self, x, cell_init, mac=False, timebase=False, tol=64, link_quality=False, score=None,
-                       vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT):
+                       vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT):
         """decode without given cells: cell_init [M] holds each carrier's scrambling init before the
         capture (3 = unknown); every carrier's cell comes from the last CRC-good BSCH over all of its
         chunk rows, and all of its rows are descrambled with it (tetra_lmac_etsi_acquire_groups, G =
@@ -257,7 +267,8 @@ class WidebandReceiver:
         link_quality=True scores every carrier's blocks with the cell acquired for it.
         score [M] int32 (C-contiguous, updated in place): the cell is chosen by the vote instead
         (tetra_lmac_etsi_vote_groups: every CRC-good BSCH weighed by its soft bits, cell_init[k] defending
-        with score[k], scores bounded by vote_cap); at most 32 chunks per carrier.  The return is the same."""
+        with score[k], scores bounded by vote_cap); at most 32 chunks per carrier.  The return is the same.
+        timebase="vote": decode's, the blocks scored with the cell acquired for the carrier."""
         state = np.array(cell_init, np.uint32)
         if state.shape != (self.plan.M,):
             raise ValueError(f"cell_init holds {state.shape} inits, the receiver has {self.plan.M} carriers")
@@ -265,17 +276,23 @@ class WidebandReceiver:
                                       score.shape == (self.plan.M,) and score.flags["C_CONTIGUOUS"]):
             raise ValueError(f"score must be a C-contiguous int32 array of {self.plan.M} (it is updated in place)")
         frames, ngood = self._decode(x, None, state, mac, timebase, tol, link_quality=link_quality, score=score,
-                                     vote_cap=vote_cap)
+                                     vote_cap=vote_cap, tdma_cap=tdma_cap)
         return frames, state, ngood
 
     def _decode(self, x, cells, state, mac, timebase=False, tol=64, tdma=None, advance=0, link_quality=False,
-                score=None, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT):
+                score=None, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_score=None,
+                tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT):
         """The chain behind decode (cells [M]) and decode_acquire (state [M], updated in place; score [M]
         int32 or None, likewise: the vote): (frames, ngood or None).  timebase: tdma [M] ETSI_TDMA (in/out; None: new streams), whose bit0
-        moves on by ``advance`` bits after the call (WidebandStream)."""
+        moves on by ``advance`` bits after the call (WidebandStream).  timebase="vote": tdma_score [M] int32
+        (in/out; None: zeros) beside it, scores bounded by tdma_cap."""
         from tetraear.core.etsi import EtsiLowerMac, run_link_quality
+        if timebase not in (False, True, "vote"):
+            raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
         if timebase and (self.m2 % 2 or tol % 2 or tol < 0):
             raise ValueError(f"timebase=True works in bits: m2 ({self.m2}) and tol ({tol}) must be even")
+        if timebase == "vote" and int(tdma_cap) <= 0:
+            raise ValueError(f"tdma_cap ({tdma_cap}) must be positive")
         hard, soft, _, ns = self.demod(x)
         M, nchunk, sm = hard.shape
         C = M * nchunk
@@ -303,17 +320,31 @@ class WidebandReceiver:
                 c.check(c.lib.tetra_lmac_etsi_acquire_groups(c.handle, *rows, nchunk, _hip.ptr(state),
                                                              _hip.ptr(ngood), *outs),
                         "tetra_lmac_etsi_acquire_groups")
-        pdus = None
+        pdus = lq = None
+        if link_quality or timebase == "vote":   # the rows are intact (origin 0); carrier k's rows with its (acquired) cell
+            lq = run_link_quality(c, soft.reshape(C, -1), hard.reshape(C, -1), 0, nchunk,
+                                  cells if state is None else state, nb, bursts, nk, blocks, t1)
         if timebase:   # merge and timebase per carrier on the device
             tdma = np.zeros(M, _hip.ETSI_TDMA) if tdma is None else tdma
             keep = np.zeros((C, _hip.ETSI_MAXB), np.int32)
             slots = np.zeros((C, _hip.ETSI_MAXB, _hip.SLOT_FIELDS), np.int32)
             npdu = np.zeros((C, _hip.ETSI_MAXJ), np.int32)
             recs = np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.PDU_FIELDS), np.int32)
-            c.check(c.lib.tetra_etsi_mac_groups(c.handle, _hip.ptr(np.ascontiguousarray(ns.reshape(-1))), C, nchunk,
-                                                self.m2 // 2, tol // 2, advance, *outs[:4], _hip.ptr(t1),
-                                                _hip.ptr(tdma), _hip.ptr(keep), _hip.ptr(slots), _hip.ptr(npdu),
-                                                _hip.ptr(recs)), "tetra_etsi_mac_groups")
+            nsf = np.ascontiguousarray(ns.reshape(-1))
+            if timebase == "vote":   # the weights and the copies' quality from the link-quality records
+                tdma_score = np.zeros(M, np.int32) if tdma_score is None else tdma_score
+                self.tvote = np.zeros((M, _hip.TV_FIELDS), np.int32)
+                c.check(c.lib.tetra_etsi_mac_vote_groups(c.handle, _hip.ptr(nsf), C, nchunk, self.m2 // 2, tol // 2,
+                                                         advance, int(tdma_cap), *outs[:4], _hip.ptr(t1),
+                                                         _hip.ptr(lq[0]), _hip.ptr(lq[1]), _hip.ptr(tdma),
+                                                         _hip.ptr(tdma_score), _hip.ptr(keep), _hip.ptr(slots),
+                                                         _hip.ptr(npdu), _hip.ptr(recs), _hip.ptr(self.tvote)),
+                        "tetra_etsi_mac_vote_groups")
+            else:
+                c.check(c.lib.tetra_etsi_mac_groups(c.handle, _hip.ptr(nsf), C, nchunk, self.m2 // 2, tol // 2, advance,
+                                                    *outs[:4], _hip.ptr(t1), _hip.ptr(tdma), _hip.ptr(keep),
+                                                    _hip.ptr(slots), _hip.ptr(npdu), _hip.ptr(recs)),
+                        "tetra_etsi_mac_groups")
             keep = keep.astype(bool)
             pdus = (slots, npdu, recs)
         else:
@@ -321,11 +352,7 @@ class WidebandReceiver:
         if mac and not timebase:   # the PDU walk is per block; a fresh timebase per row, its slots not reported
             pdus = EtsiLowerMac(mac=True)._run_mac(c, C, np.ascontiguousarray(ns.reshape(-1)), nb, bursts, nk, blocks,
                                                   t1, None)
-        lq = None
-        if link_quality:   # the rows are intact (origin 0); carrier k's rows with its (acquired) cell
-            lq = run_link_quality(c, soft.reshape(C, -1), hard.reshape(C, -1), 0, nchunk,
-                                  cells if state is None else state, nb, bursts, nk, blocks, t1)
-        frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1, pdus, lq)
+        frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1, pdus, lq if link_quality else None)
         if mac and not timebase:
             for fr in frames:
                 for f in fr:
@@ -365,6 +392,10 @@ class WidebandStream:
     (implies it): the frames carry ``tn`` / ``fn`` / ``mn`` / ``slot_flags`` from one TDMA timebase per
     carrier, carried from piece to piece in ``tdma`` [M] (reset() clears it): a buffer's carried tail
     is decoded again behind the anchor, which places those bursts without moving it.
+    ``timebase="vote"``: the timebases by tetra_etsi_mac_vote_groups (WidebandReceiver.decode): the score
+    each carrier's slot grid has gathered is carried beside ``tdma`` in ``tdma_score`` [M] and read as
+    ``tdma_scores`` (reset() clears it); ``tdma_cap`` bounds it.  Within a buffer the best copy of a burst
+    is kept; the choice between a burst's copies in two successive buffers stays "first decoded" (``last``).
     ``link_quality=True``: the frames and blocks carry the link-quality keys (WidebandReceiver.decode).
     ``vote=True`` (acquisition only): a carrier's cell is chosen by the vote over each buffer's BSCH
     blocks (WidebandReceiver.decode_acquire(score=...)), the score it gathers carried from piece to piece
@@ -378,9 +409,15 @@ class WidebandStream:
     CARRY_Y = 2 * BURST_SAMPLES
 
     def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False, timebase=False,
-                 link_quality=False, vote=False, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT):
+                 link_quality=False, vote=False, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT,
+                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT):
+        if timebase not in (False, True, "vote"):
+            raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
         self.rx = WidebandReceiver(fs, M, m2, oversample)
         self.acquire, self.mac, self.timebase = cells is None, bool(mac), bool(timebase)
+        self.tdma_vote, self.tdma_cap = timebase == "vote", int(tdma_cap)
+        if self.tdma_vote and self.tdma_cap <= 0:
+            raise ValueError(f"tdma_cap ({tdma_cap}) must be positive")
         self.link_quality = bool(link_quality)
         self.vote, self.vote_cap = bool(vote), int(vote_cap)
         if self.vote and not self.acquire:
@@ -407,6 +444,11 @@ class WidebandStream:
         """vote=True: the score each carrier's cell has gathered ([M] int32, a copy); else None."""
         return None if self.cell_score is None else self.cell_score.copy()
 
+    @property
+    def tdma_scores(self):
+        """timebase="vote": the score each carrier's timebase has gathered ([M] int32, a copy); else None."""
+        return None if self.tdma_score is None else self.tdma_score.copy()
+
     def reset(self):
         self.tail = np.zeros(0, np.complex64)
         self.y0 = 0                                    # stream position of the buffer's first output
@@ -418,13 +460,15 @@ class WidebandStream:
         self.cell_score = np.zeros(self.M, np.int32) if self.vote else None   # the vote's score per carrier
         # timebase: each carrier's tetra_etsi_tdma; bit0 = the stream bit of the buffer's first output
         self.tdma = np.zeros(self.M, _hip.ETSI_TDMA) if self.timebase else None
+        self.tdma_score = np.zeros(self.M, np.int32) if self.tdma_vote else None   # timebase="vote"
 
     def _decode_buffer(self, buf, advance=0):
         if self.timebase:
             state = np.array(self.cell_state, np.uint32) if self.acquire else None
-            frames, ngood = self.rx._decode(buf, self._cells, state, True, True, 64, self.tdma, advance,
-                                            link_quality=self.link_quality, score=self.cell_score,
-                                            vote_cap=self.vote_cap)
+            frames, ngood = self.rx._decode(buf, self._cells, state, True, "vote" if self.tdma_vote else True, 64,
+                                            self.tdma, advance, link_quality=self.link_quality,
+                                            score=self.cell_score, vote_cap=self.vote_cap,
+                                            tdma_score=self.tdma_score, tdma_cap=self.tdma_cap)
             if self.acquire:
                 self.cell_state = state
                 self.acquired |= ngood > 0
@@ -453,7 +497,7 @@ class WidebandStream:
         T = max(0, (n72 - self.CARRY_Y) // self.ups) * self.per   # the next buffer starts here
         dy = self.ups * (T // self.per)                            # ... this many 72 kHz outputs on
         assert not self.timebase or dy % 2 == 0, "a buffer starts a whole number of bits after the previous one"
-        if n72 < 16 and self.timebase:
+        if n72 < 16 and self.timebase:   # (nothing decoded: no burst, no expiry, the scores stay)
             self.tdma["bit0"] += dy // 2
         if n72 >= 16:
             for k, fr in enumerate(self._decode_buffer(buf, dy // 2)):
@@ -510,7 +554,9 @@ class BenchStep:
     by tetra_lmac_etsi_vote_groups, the scores in cell_score [M].  TETRA_WB_MAC=timebase: the
     capture is synthesised on the slot grid and tetra_etsi_mac_groups follows the lower MAC on the same
     context (PDU headers, the merge of each carrier's chunk rows, one TDMA timebase per carrier resident
-    on the device; every step decodes the same capture, so bit0 does not advance).  TETRA_WB_IQ=sc16
+    on the device; every step decodes the same capture, so bit0 does not advance).  TETRA_WB_MAC=vote: the
+    same with tetra_etsi_link_quality and then tetra_etsi_mac_vote_groups in its place (the scores in
+    tdma_score [M], the ballots in tvote [M, 4]; for tools/probe_tdma_vote.py).  TETRA_WB_IQ=sc16
     (default cf32): the capture is resident as the radio's int16 pairs -- the synthesised sum of 800
     carriers scaled by the smallest power of two that brings it into full scale, rounded -- and the
     channeliser and the waterfall take it as TETRA_SC16."""
@@ -550,9 +596,10 @@ class BenchStep:
         self.kinds = torch.empty((M, nb), dtype=torch.int32, device=device)
         self.payload = torch.empty((M, nb, 2, 268), dtype=torch.uint8, device=device)
         mac = os.environ.get("TETRA_WB_MAC", "")
-        if mac not in ("", "timebase"):
-            raise ValueError(f"TETRA_WB_MAC={mac!r}: timebase, or unset")
-        self.timebase, self.seed = mac == "timebase", seed
+        if mac not in ("", "timebase", "vote"):
+            raise ValueError(f"TETRA_WB_MAC={mac!r}: timebase, vote, or unset")
+        self.timebase, self.seed = mac in ("timebase", "vote"), seed
+        self.tdma_vote = mac == "vote"   # the timebase by tetra_etsi_mac_vote_groups
         if self.timebase:
             c.check(c.lib.tetra_synth_set_grid(c.handle, 1), "synth_set_grid")
         c.check(c.lib.tetra_synth_wideband(c.handle, self.plan.c, Nw, seed, snr_db, 300.0, _hip.ptr(self.x),
@@ -566,6 +613,7 @@ class BenchStep:
             self.x = torch.round(self.x * (32768.0 * 2.0 ** -self.sc16_k)).clamp_(-32768, 32767).to(torch.int16)
         # every chunk of carrier k uses carrier k's scrambling code
         self.cells = cells.repeat_interleave(self.nchunk).contiguous()
+        self.cells_carrier = cells
         mode = os.environ.get("TETRA_WB_CELLS", "given")
         if mode not in ("given", "acquire", "vote"):
             raise ValueError(f"TETRA_WB_CELLS={mode!r}: given, acquire or vote")
@@ -605,6 +653,11 @@ class BenchStep:
             self.npdu = torch.zeros((self.C, _hip.ETSI_MAXJ), dtype=torch.int32, device=device)
             self.pdus = torch.zeros((self.C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.PDU_FIELDS), dtype=torch.int32,
                                     device=device)
+            if self.tdma_vote:
+                self.bq = torch.zeros((self.C, _hip.ETSI_MAXB, _hip.LQ_FIELDS), dtype=torch.int32, device=device)
+                self.kq = torch.zeros((self.C, _hip.ETSI_MAXJ, _hip.LQ_FIELDS), dtype=torch.int32, device=device)
+                self.tdma_score = torch.zeros(M, dtype=torch.int32, device=device)
+                self.tvote = torch.zeros((M, _hip.TV_FIELDS), dtype=torch.int32, device=device)
             torch.cuda.current_stream(device).synchronize()
         self.nfr = Nw // 2048   # waterfall rows of the capture (2048-pt Hann frames, hop 2048)
         self.wf = torch.empty((self.nfr, 2048), dtype=torch.float32, device=device)
@@ -689,6 +742,25 @@ class BenchStep:
                                                _hip.ptr(self.hard), _hip.ptr(self.nsym), self.sm, None),
                 "etsi_timing_chunks")
 
+    def _quality(self, c):
+        """tetra_etsi_link_quality on the rows the lower MAC read (intact: origin 0), every carrier's rows
+        with its configured or acquired cell."""
+        c.check(c.lib.tetra_etsi_link_quality(c.handle, _hip.ptr(self.soft), _hip.ptr(self.hard), self.C, self.sm, 0,
+                                              self.nchunk, _hip.ptr(self.cell_state if self.acquire else
+                                                                    self.cells_carrier),
+                                              _hip.ptr(self.nburst), _hip.ptr(self.bursts), _hip.ptr(self.nblock),
+                                              _hip.ptr(self.blocks), _hip.ptr(self.type1), _hip.ptr(self.bq),
+                                              _hip.ptr(self.kq)), "etsi_link_quality")
+
+    def _mac_vote(self, c):
+        c.check(c.lib.tetra_etsi_mac_vote_groups(c.handle, _hip.ptr(self.nsym), self.C, self.nchunk, self.m2 // 2, 32, 0,
+                                                 _hip.TETRA_TDMA_VOTE_CAP_DEFAULT, _hip.ptr(self.nburst),
+                                                 _hip.ptr(self.bursts), _hip.ptr(self.nblock), _hip.ptr(self.blocks),
+                                                 _hip.ptr(self.type1), _hip.ptr(self.bq), _hip.ptr(self.kq),
+                                                 _hip.ptr(self.tdma), _hip.ptr(self.tdma_score), _hip.ptr(self.keep),
+                                                 _hip.ptr(self.slots), _hip.ptr(self.npdu), _hip.ptr(self.pdus),
+                                                 _hip.ptr(self.tvote)), "etsi_mac_vote_groups")
+
     def _mac(self, c):
         c.check(c.lib.tetra_etsi_mac_groups(c.handle, _hip.ptr(self.nsym), self.C, self.nchunk, self.m2 // 2, 32, 0,
                                             _hip.ptr(self.nburst), _hip.ptr(self.bursts), _hip.ptr(self.nblock),
@@ -698,7 +770,10 @@ class BenchStep:
 
     def _lmac(self, c):
         self._lmac_rows(c)
-        if self.timebase:
+        if self.tdma_vote:
+            self._quality(c)
+            self._mac_vote(c)
+        elif self.timebase:
             self._mac(c)
 
     def _lmac_rows(self, c):
@@ -789,7 +864,7 @@ class BenchStep:
                 "pipeline": self.pipelined,
                 # (bench.py adds cells_mode itself only to the config it builds for steps without one)
                 **({"cells": self.cells_mode} if self.acquire else {}),
-                **({"mac": "timebase"} if self.timebase else {}),
+                **({"mac": "vote" if self.tdma_vote else "timebase"} if self.timebase else {}),
                 **({"iq": "sc16", "sc16_scale": f"2^-{self.sc16_k}"} if self.iq_name == "sc16" else {})}
 
     def realtime_channels(self, value_msps):
@@ -816,9 +891,16 @@ class BenchStep:
         tb = {}
         if self.timebase:
             dkeep = self.keep.cpu().numpy().astype(bool) & (np.arange(keep.shape[1])[None, :] < nb[:, None])
-            if not np.array_equal(dkeep, keep):
+            if self.tdma_vote:   # the vote keeps a burst's best copy: one per burst as merge_chunks, maybe another
+                if dkeep.sum() != keep.sum():
+                    raise RuntimeError("tetra_etsi_mac_vote_groups keeps another number of bursts than merge_chunks")
+                tb = dict(keep_differs=int((dkeep != keep).sum() // 2), tvote=self.tvote.cpu().numpy().sum(axis=0).tolist())
+                keep = dkeep
+                live = np.arange(kb.shape[1])[None, :] < np.clip(nk, 0, kb.shape[1])[:, None]
+                kb = live & np.take_along_axis(keep, np.clip(blocks[..., 2], 0, keep.shape[1] - 1), axis=1)
+            elif not np.array_equal(dkeep, keep):
                 raise RuntimeError("tetra_etsi_mac_groups' keep differs from merge_chunks'")
-            tb = self._timebase_quality(keep, nk, blocks)
+            tb.update(self._timebase_quality(keep, nk, blocks))
         slots = self.plan.M * self.ck.rowlen / BURST_SAMPLES
         return dict(blocks=int(kb.sum()), crc_ok=int((blocks[..., 1].astype(bool) & kb).sum()),
                     bursts=int(keep.sum()), decoded_frac=round(float(keep.sum()) / slots, 4),
