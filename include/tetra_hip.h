@@ -764,6 +764,53 @@ int tetra_etsi_mac_vote_groups(tetra_ctx *ctx, const int32_t *nsym, size_t C, si
                                int32_t *keep, int32_t *slots, int32_t *npdu, int32_t *pdus,
                                int32_t *tvote /*[C/G][TETRA_TV_FIELDS] out*/);
 
+/* ---------------------------------------------------------------- traffic slots (a new symbol of ABI
+ * version 2; nothing existing changed shape).  The reference's capture loop builds the speech codec's
+ * input from every frame that looks like traffic (_extract_voice_slot_from_symbols); the ETSI chain
+ * reported such a slot only as "SCH/F, CRC bad".  tetra_etsi_traffic classifies every burst of a
+ * lower-MAC call and copies out, for the bursts the control decoders could not read, what the speech
+ * codec's own channel decoder consumes: the block fields' type-4 soft bits, i.e. descrambled with the
+ * cell's sequence and nothing more (TCH is exported, not decoded).  All exact integers, restated in
+ * tests/_etsi_traffic_model.py.
+ *
+ * Inputs: those of tetra_etsi_link_quality, with the same meaning of origin_bits, G and cell_init; the
+ * rows must be the ones the lower-MAC call read, still intact.  slots [C][MAXB][TETRA_SLOT_FIELDS] and
+ * keep [C][MAXB] are the outputs of tetra_etsi_mac / _groups / _vote_groups for the same rows, or NULL.
+ *
+ * tq [C][MAXB][TETRA_TQ_FIELDS] and tch [C][MAXB][TETRA_TCH_BITS], for b < nburst[c] (clamped to
+ * 0..MAXB; nothing past it written in either).  The first of these that applies decides CLASS:
+ *   a. an invalid burst (kind outside 0..2, or row bits origin_bits + start .. + 510 not inside the
+ *      row's 2 stride bits): nothing of it is read, tq reads -1, -1, -1, -1, tch is not written;
+ *   b. keep != NULL and keep[c][b] == 0 (the copy not chosen): NONE;
+ *   c. kind 2 (synchronisation burst): NONE;
+ *   d. slots != NULL and slots[c][b][TETRA_SLOT_FN] == 18 (the control frame): CONTROL;
+ *   e. kind 0: CONTROL if some j < nblock[c] (clamped to 0..MAXJ) has blocks[c][j] == (kind 0,
+ *      crc_ok != 0, burst b, index 0), otherwise FULL;
+ *   f. kind 1, with g0 / g1 the same test for (kind 1, index 0) / (kind 1, index 1): both CONTROL, g0
+ *      only HALF (the first half was stolen and decoded, the second is a traffic half slot), otherwise
+ *      LOST.
+ * NONE, CONTROL and LOST set NBITS, WSUM and NZERO to 0 and leave tch unwritten.  FULL exports n = 432
+ * values, s_i the soft byte at burst bit 14 + i for i < 216 and at 282 + (i - 216) from there on; HALF
+ * n = 216, s_i at burst bit 282 + i.  With q_i bit i of the scrambling sequence of cell_init[c / G]
+ * (every block is scrambled from the sequence's start), tch[c][b][i] = q_i ? (s_i == -128 ? 127 : -s_i)
+ * : s_i for i < n; bytes from n on are not written.  NBITS = n, WSUM = the sum of |tch_i| (|-128| =
+ * 128), NZERO = the count of tch_i == 0.  The chain's sign convention is kept: positive means bit 0.
+ *
+ * Without the AACH a FULL slot is a candidate: a control burst lost to noise looks the same.  WSUM and
+ * the timebase are what a caller gates on.
+ *
+ * C == 0, stride == 0, G == 0, C % G != 0, origin_bits < 0 or a NULL required array: TETRA_E_INVALID,
+ * nothing written.  Host or device pointers; with device pointers the call enqueues one kernel on the
+ * context stream and returns without waiting (no allocation, no synchronising copy). */
+enum { TETRA_TQ_CLASS = 0, TETRA_TQ_NBITS, TETRA_TQ_WSUM, TETRA_TQ_NZERO, TETRA_TQ_FIELDS = 4 };
+enum { TETRA_TCH_NONE = 0, TETRA_TCH_CONTROL, TETRA_TCH_FULL, TETRA_TCH_HALF, TETRA_TCH_LOST };
+#define TETRA_TCH_BITS 432
+int tetra_etsi_traffic(tetra_ctx *ctx, const int8_t *softbits, size_t C, size_t stride, int32_t origin_bits,
+                       size_t G, const uint32_t *cell_init /*[C/G]*/,
+                       const int32_t *nburst, const int32_t *bursts, const int32_t *nblock, const int32_t *blocks,
+                       const int32_t *slots /*[C][MAXB][4] or NULL*/, const int32_t *keep /*[C][MAXB] or NULL*/,
+                       int32_t *tq /*[C][MAXB][4]*/, int8_t *tch /*[C][MAXB][432]*/);
+
 /* The ETSI receiver's AFC mixer on a streaming window: out [C][N] cf32 = iq (cf32 rows ld samples
  * apart) x exp(-j 2 pi f (n0 + n) / fs), n0 = the window's first sample in the capture (frequency_shift's
  * float64 arithmetic, processor.py:85-100, with one continuous phase across windows); mix_c [C] as

@@ -1,5 +1,5 @@
 // etsi_coding.h -- the EN 300 392-2 channel-coding constants the lower-MAC units share (etsi_lmac.hip,
-// etsi_quality.hip): block kinds, burst patterns, the puncturer, the CRC-16 and the scrambler as
+// etsi_quality.hip, etsi_traffic.hip): block kinds, burst patterns, the puncturer, the CRC-16 and the scrambler as
 // linear tables.  Each unit gets its own copy (the unit's anonymous namespace).
 #pragma once
 #include "common.h"
@@ -74,5 +74,19 @@ constexpr ScrMask make_scr_mask() {
     return m;
 }
 __constant__ ScrMask SCR_MASK = make_scr_mask();
+
+// the post-passes over the rows a lower-MAC call read (etsi_quality.hip, etsi_traffic.hip)
+__device__ __forceinline__ uint32_t load_u32(const void *p) {   // any alignment
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+
+// whether burst b of the row lies in it: kind 0..2 and row bits [origin + start, + 510) inside 2 stride
+__device__ __forceinline__ bool burst_ok(const int32_t *bu, int b, long origin, long row_bits, long &p0, int &kind) {
+    kind = bu[2 * b + 1];
+    p0 = origin + (long)bu[2 * b];
+    return kind >= 0 && kind <= 2 && p0 >= 0 && p0 + 510 <= row_bits;
+}
 
 }  // namespace

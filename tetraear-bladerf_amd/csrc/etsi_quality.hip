@@ -47,12 +47,6 @@ constexpr bool punct_form_ok() {
 }
 static_assert(punct_form_ok(), "puncturer");
 
-__device__ __forceinline__ uint32_t load_u32(const void *p) {   // any alignment
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-
 __device__ __forceinline__ uint32_t group_xor(uint32_t v) {
 #pragma unroll
     for (int m = LQ_LANES / 2; m >= 1; m >>= 1) v ^= (uint32_t)__shfl_xor((int)v, m, LQ_LANES);
@@ -67,13 +61,6 @@ __device__ __forceinline__ uint32_t group_sum(uint32_t v) {
 __device__ __forceinline__ int hard_bit(const uint8_t *hrow, long p) {   // as the burst scan reads it
     const uint32_t h = hrow[p >> 1];
     return (int)((p & 1) ? h & 1u : (h >> 1) & 1u);
-}
-
-// whether burst b of the row lies in it: kind 0..2 and row bits [origin + start, + 510) inside 2 stride
-__device__ __forceinline__ bool burst_ok(const int32_t *bu, int b, long origin, long row_bits, long &p0, int &kind) {
-    kind = bu[2 * b + 1];
-    p0 = origin + (long)bu[2 * b];
-    return kind >= 0 && kind <= 2 && p0 >= 0 && p0 + 510 <= row_bits;
 }
 
 // Burst b of a row by one group of 16 lanes: its record to o[0..3].

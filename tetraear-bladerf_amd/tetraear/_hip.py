@@ -89,6 +89,10 @@ TETRA_ETSI_VOTE_CAP_DEFAULT = 8 * 120 * 127
 # BSCH blocks; the tvote record; FLAGS bit 2 of a slot row, "own SYNC outvoted"
 TETRA_TDMA_VOTE_CAP_DEFAULT = 4 * 120 * 127
 TV_BALLOTS, TV_AGREED, TV_OUTVOTED, TV_WON, TV_FIELDS = range(5)
+# tetra_etsi_traffic (include/tetra_hip.h): the burst records tq, the classes and the soft bits a slot exports
+TQ_CLASS, TQ_NBITS, TQ_WSUM, TQ_NZERO, TQ_FIELDS = range(5)
+TCH_NONE, TCH_CONTROL, TCH_FULL, TCH_HALF, TCH_LOST = range(5)
+TCH_BITS = 432
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -169,6 +173,8 @@ def _bind(L):
                                               _vp, _vp]),
         "tetra_etsi_link_quality": (_i32, [_vp, _vp, _vp, _sz, _sz, ctypes.c_int32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp]),
+        "tetra_etsi_traffic": (_i32, [_vp, _vp, _sz, _sz, ctypes.c_int32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp]),
         "tetra_etsi_mix": (_i32, [_vp, _vp, _sz, _sz, _sz, _vp, ctypes.c_double, ctypes.c_int64, _vp]),
         "tetra_etsi_decode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
         "tetra_etsi_encode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp]),

@@ -89,7 +89,8 @@ class TetraDecoder:
     """Decodes TETRA frames from demodulated symbols (decoder.py:16)."""
 
     def __init__(self, key_manager=None, auto_decrypt: bool = True, mode=None, mac: bool = False,
-                 link_quality: bool = False, vote: bool = False, timebase_vote: bool = False):
+                 link_quality: bool = False, vote: bool = False, timebase_vote: bool = False,
+                 traffic: bool = False):
         self.SYNC_PATTERN = [0, 1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0,
                              1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0]
         self.FRAME_LENGTH = 510
@@ -106,6 +107,8 @@ class TetraDecoder:
         self.etsi_vote = bool(vote)   # mode="etsi": the cell by the soft-weighted vote (EtsiLowerMac(vote=True))
         # mode="etsi", mac=True: the timebase by the vote on SYNC bursts (EtsiLowerMac(timebase_vote=True))
         self.etsi_timebase_vote = bool(timebase_vote)
+        # mode="etsi": every frame's usage and a traffic slot's descrambled soft bits (EtsiLowerMac(traffic=True))
+        self.etsi_traffic = bool(traffic)
 
     # ------------------------------------------------------------------ keys and the reference's rest
     def set_keys(self, keys):
@@ -377,7 +380,9 @@ class TetraDecoder:
         burst_crc = every block's CRC-16, the frame header and type from the first MAC block, and the
         compat drop rule (no PDU and a failed CRC drops the burst).  The burst's first PDU goes
         through the compat MAC stage ('mac_pdu', 'encrypted', 'encryption_algorithm'); all of them
-        are on 'mac_pdus'.  The ETSI details stay on the frame: 'blocks', 'burst', 'burst_kind'."""
+        are on 'mac_pdus'.  The ETSI details stay on the frame: 'blocks', 'burst', 'burst_kind'.
+        With traffic=True the frames carry 'usage' / 'traffic', and a burst exported for the codec is
+        exempt from the drop rule: a traffic slot has no PDU and fails the control CRC by nature."""
         from tetraear.core.protocol import BurstType, TetraBurst
         rows, owner = [], []   # one row per CRC-good SCH/F / SCH/HD block, in order
         for i, f in enumerate(raw):
@@ -402,6 +407,7 @@ class TetraDecoder:
             frame.update({k: f[k] for k in ("tn", "fn", "mn", "slot_flags") if k in f})   # EtsiLowerMac(mac=True)
             frame.update({k: f[k] for k in ("training_errors", "edge_errors", "soft_sum", "saturated")
                           if k in f})   # EtsiLowerMac(link_quality=True); the blocks carry theirs
+            frame.update({k: f[k] for k in ("usage", "traffic") if k in f})   # EtsiLowerMac(traffic=True)
             while k < len(owner) and owner[k] == i:   # the MAC state advances in block order
                 pdu = self.protocol_parser.mac_state(fields[k], data[k])
                 if pdu is not None:
@@ -412,7 +418,9 @@ class TetraDecoder:
                                training_sequence=np.zeros(0, np.int64),
                                data_bits=np.concatenate([np.asarray(b["bits"]) for b in f["blocks"]]).astype(np.int64),
                                crc_ok=crc_ok, colour_code=self._etsi.colour_code or 0)
-            frame = self._mac_stage(frame, burst, pdus[i][0] if pdus[i] else None)
+            staged = self._mac_stage(frame, burst, pdus[i][0] if pdus[i] else None)
+            # traffic=True: a slot exported for the codec is kept though its control CRC failed and it has no PDU
+            frame = staged if staged or f.get("traffic") is None else frame
             if frame:
                 frame['mac_pdus'] = [{'type': p.pdu_type.name, 'encrypted': p.encrypted, 'address': p.address,
                                       'length': p.length, 'data': p.data} for p in pdus[i]]
@@ -423,5 +431,5 @@ class TetraDecoder:
         if self._etsi is None:
             from tetraear.core.etsi import EtsiLowerMac
             self._etsi = EtsiLowerMac(mac=self.etsi_mac, link_quality=self.etsi_link_quality, vote=self.etsi_vote,
-                                      timebase_vote=self.etsi_timebase_vote)
+                                      timebase_vote=self.etsi_timebase_vote, traffic=self.etsi_traffic)
         return self._etsi

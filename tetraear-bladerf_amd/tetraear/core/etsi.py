@@ -12,6 +12,9 @@ multiframe of every burst and the MAC PDU headers of every CRC-good block (EN 30
 With ``link_quality=True`` tetra_etsi_link_quality (k_etsi_quality) follows it too: per burst the known
 bits that came out wrong and the soft bits' strength, per CRC-good block the channel bits the decoder
 corrected.
+With ``traffic=True`` tetra_etsi_traffic (k_etsi_traffic) follows them: every burst gets a ``usage``, and
+a slot the control decoders could not read comes out as descrambled type-4 soft bits, which
+``codec_frame`` lays out as the speech codec's input frame.
 """
 import numpy as np
 
@@ -127,6 +130,93 @@ def carrier_quality(frames):
     return out
 
 
+USAGE_NAMES = {_hip.TCH_CONTROL: "control", _hip.TCH_FULL: "traffic", _hip.TCH_HALF: "stolen", _hip.TCH_LOST: "lost"}
+CODEC_WORDS, CODEC_HEADER = 690, 0x6B21
+# the 432 values of a codec frame lie at these words (word 0 the header, every other word 0)
+CODEC_RUNS = ((1, 114), (116, 114), (231, 114), (346, 90))
+
+
+def run_traffic(c, soft, origin, G, cells, nb, bursts, nk, blocks, slots=None, keep=None):
+    """tetra_etsi_traffic on host arrays (soft [C, 2 stride]): (tq [C, MAXB, 4], -1 where not written,
+    tch [C, MAXB, 432])."""
+    C, stride = soft.shape[0], soft.shape[1] // 2
+    cells = np.ascontiguousarray(cells, np.uint32)
+    tq = np.full((C, _hip.ETSI_MAXB, _hip.TQ_FIELDS), -1, np.int32)
+    tch = np.zeros((C, _hip.ETSI_MAXB, _hip.TCH_BITS), np.int8)
+    c.check(c.lib.tetra_etsi_traffic(c.handle, _hip.ptr(soft), C, stride, origin, G, _hip.ptr(cells), _hip.ptr(nb),
+                                     _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(slots), _hip.ptr(keep),
+                                     _hip.ptr(tq), _hip.ptr(tch)), "tetra_etsi_traffic")
+    return tq, tch
+
+
+def traffic_keys(rec, tch, burst_kind, has_cell=True):
+    """One burst record of tetra_etsi_traffic and its soft row as the keys a frame gains: ``usage``
+    ("sync", "control", "traffic", "stolen" -- a half slot behind a stolen, decoded half -- "lost", or
+    None: an invalid burst, a copy not kept, or a channel without a cell) and ``traffic`` (None, or
+    dict(bits, soft int8 [bits], soft_sum, erased))."""
+    r = [int(v) for v in rec]
+    cls = r[_hip.TQ_CLASS]
+    if not has_cell or cls < 0:
+        return {"usage": None, "traffic": None}
+    if cls == _hip.TCH_NONE:   # a synchronisation burst, or (with keep) the copy not chosen
+        return {"usage": "sync" if burst_kind == 2 else None, "traffic": None}
+    out = {"usage": USAGE_NAMES[cls], "traffic": None}
+    if cls in (_hip.TCH_FULL, _hip.TCH_HALF):
+        n = r[_hip.TQ_NBITS]
+        out["traffic"] = {"bits": n, "soft": np.array(tch[:n], np.int8), "soft_sum": r[_hip.TQ_WSUM],
+                          "erased": r[_hip.TQ_NZERO]}
+    return out
+
+
+def codec_frame(soft, polarity="reference", block_markers=False):
+    """The speech codec's input frame of one full traffic slot: 1380 bytes, 690 little-endian int16
+    words -- word 0 = 0x6B21, the 432 values at words 1..114, 116..229, 231..344 and 346..435, every
+    other word 0 -- as the reference's writer lays them out (ui/modern.py:2369-2417; pinned word for
+    word by tests/golden/g6_voice.npz).  ``soft``: the 432 type-4 soft values of a "traffic" frame
+    (frame["traffic"]["soft"]; positive means bit 0).  ``polarity="reference"`` writes clamp(-soft, -127,
+    127), bit 1 positive as the reference's writer has it; ``"inverted"`` writes clamp(soft, -127, 127).
+    ``block_markers=True`` also writes 0x6B21 + i at words 115 i, i = 1..5.  The inverted polarity and
+    the markers are written from memory of the ETSI codec's own file writer: no fixture pins them.
+    216 values (a half slot) raise ValueError: the reference defines no half-slot frame."""
+    s = np.asarray(soft)
+    if s.ndim != 1 or len(s) != _hip.TCH_BITS:
+        raise ValueError(f"codec_frame takes the {_hip.TCH_BITS} soft values of a full slot, not {s.shape}")
+    if polarity not in ("reference", "inverted"):
+        raise ValueError(f"polarity {polarity!r}: 'reference' or 'inverted'")
+    v = s.astype(np.int32)
+    v = np.clip(-v if polarity == "reference" else v, -127, 127)
+    w = np.zeros(CODEC_WORDS, "<i2")
+    w[0] = CODEC_HEADER
+    at = 0
+    for first, n in CODEC_RUNS:
+        w[first:first + n] = v[at:at + n]
+        at += n
+    if block_markers:
+        for i in range(1, 6):
+            w[115 * i] = CODEC_HEADER + i
+    return w.tobytes()
+
+
+def traffic_streams(frames):
+    """One carrier's frames -> {tn: [frame, ...]} of its "traffic" frames in time order (the order
+    given); tn is None for frames without a timebase."""
+    out = {}
+    for f in frames:
+        if f.get("usage") == "traffic":
+            out.setdefault(f.get("tn"), []).append(f)
+    return out
+
+
+def slot_usage(frames):
+    """One carrier's frames -> {tn: {usage: count}} (tn None without a timebase): the read-out a
+    scanner ranks carriers by."""
+    out = {}
+    for f in frames:
+        d = out.setdefault(f.get("tn"), {})
+        d[f.get("usage")] = d.get(f.get("usage"), 0) + 1
+    return out
+
+
 class EtsiLowerMac:
     """Lower MAC of the ETSI chain.  With a cell (mcc, mnc, colour_code) every channel is
     descrambled with it.  Without one the receiver acquires the cell itself: each chunk's BSCH
@@ -165,12 +255,23 @@ class EtsiLowerMac:
     marks a burst whose own SYNC was outvoted.  tetra_etsi_link_quality runs first for the weights (the
     streaming origin for streaming rows; its keys reach the frames only with ``link_quality=True``).  The
     one difference from tetra_etsi_mac on a stream without contradictions: a burst behind the anchor does
-    not drop the lock (tetra_etsi_mac_groups' rule 1)."""
+    not drop the lock (tetra_etsi_mac_groups' rule 1).
+
+    ``traffic=True``: tetra_etsi_traffic runs after the lower MAC (and after the MAC call when
+    ``mac=True``, whose slots it is given: frame 18 never carries traffic) on the rows it read.  Every
+    frame gains ``usage`` and ``traffic`` (traffic_keys): a normal burst whose blocks the control decoders
+    could not read comes out as its 432 (216 behind a stolen half) descrambled type-4 soft bits, positive
+    meaning bit 0 -- what the speech codec's channel decoder consumes (codec_frame).  Without the AACH
+    such a slot is a candidate: a control burst lost to noise looks the same, and ``soft_sum`` and the
+    timebase are what a caller gates on.  In acquisition mode a channel without a cell yet reports
+    ``usage`` None.  decode_stream alternates two sets of rows as with ``link_quality=True``.  Everything
+    else in the frames is unchanged."""
 
     def __init__(self, mcc=None, mnc=None, colour_code=None, mac=False, link_quality=False, vote=False,
                  vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, timebase_vote=False,
-                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT):
+                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False):
         self.mac = bool(mac)
+        self.traffic = bool(traffic)
         self.link_quality = bool(link_quality)
         self.timebase_vote, self.tdma_cap = bool(timebase_vote), int(tdma_cap)
         if self.timebase_vote and not self.mac:
@@ -264,9 +365,9 @@ class EtsiLowerMac:
                     "tetra_lmac_etsi")
             used = cells
         lq = self._run_quality(c, soft, hard, 0, used, nb, bursts, nk, blocks, t1)
-        return self._frames(C, nb, bursts, nk, blocks, t1,
-                            self._run_mac(c, C, nsym, nb, bursts, nk, blocks, t1, None, lq),
-                            lq if self.link_quality else None)
+        mac = self._run_mac(c, C, nsym, nb, bursts, nk, blocks, t1, None, lq)
+        tr = self._run_traffic(c, soft, 0, used, nb, bursts, nk, blocks, mac, used is self.cell_state)
+        return self._frames(C, nb, bursts, nk, blocks, t1, mac, lq if self.link_quality else None, tr)
 
     def _score(self, C):
         """cell_score for C channels (vote=True): zeros when new or of another length."""
@@ -280,6 +381,15 @@ class EtsiLowerMac:
         if not (self.link_quality or self.timebase_vote):
             return None
         return run_link_quality(c, soft, hard, origin, 1, cells, nb, bursts, nk, blocks, t1)
+
+    def _run_traffic(self, c, soft, origin, cells, nb, bursts, nk, blocks, mac, acquiring):
+        """tetra_etsi_traffic on the rows the lower-MAC call read (traffic=True; else None): (tq, tch,
+        has_cell [C]).  mac: None or the MAC call's (slots, npdu, pdus); acquiring: the cells are the
+        acquisition state, so a channel has one only once a BSCH decoded."""
+        if not self.traffic:
+            return None
+        tq, tch = run_traffic(c, soft, origin, 1, cells, nb, bursts, nk, blocks, None if mac is None else mac[0])
+        return tq, tch, self.acquired.copy() if acquiring else np.ones(len(nb), bool)
 
     def _run_mac(self, c, C, nsym, nb, bursts, nk, blocks, t1, tdma, lq=None, score=None):
         """tetra_etsi_mac on the lower MAC's outputs (mac=True; else None): (slots, npdu, pdus).
@@ -372,7 +482,8 @@ class EtsiLowerMac:
             self._alt = None
         srow, hrow, lead = self._rows
         stride = hrow.shape[1]
-        intact = self.link_quality or self.timebase_vote   # the quality pass reads the rows after the call
+        # the quality and traffic passes read the rows after the call
+        intact = self.link_quality or self.timebase_vote or self.traffic
         if intact and self._alt is None:
             self._alt = (np.zeros_like(srow), np.zeros_like(hrow))
         hrow[:, R:R + smax] = hard
@@ -394,14 +505,14 @@ class EtsiLowerMac:
             self.tdma_score = None
         if self.timebase_vote and self.tdma_score is None:
             self.tdma_score = np.zeros(C, np.int32)
-        return self._frames(C, nb, bursts, nk, blocks, t1,
-                            self._run_mac(_hip.ctx(), C, nsym, nb, bursts, nk, blocks, t1, self._tdma, lq,
-                                          self.tdma_score), lq if self.link_quality else None)
+        mac = self._run_mac(_hip.ctx(), C, nsym, nb, bursts, nk, blocks, t1, self._tdma, lq, self.tdma_score)
+        tr = self._run_traffic(_hip.ctx(), srow, 2 * R, used, nb, bursts, nk, blocks, mac, used is self.cell_state)
+        return self._frames(C, nb, bursts, nk, blocks, t1, mac, lq if self.link_quality else None, tr)
 
     @staticmethod
-    def _frames(C, nb, bursts, nk, blocks, t1, mac=None, lq=None):
+    def _frames(C, nb, bursts, nk, blocks, t1, mac=None, lq=None, tr=None):
         """mac: None, or tetra_etsi_mac's (slots, npdu, pdus) for the same call; lq: None, or
-        tetra_etsi_link_quality's (bq, kq)."""
+        tetra_etsi_link_quality's (bq, kq); tr: None, or tetra_etsi_traffic's (tq, tch, has_cell [C])."""
         out = []
         for ch in range(C):
             frames = []
@@ -429,6 +540,8 @@ class EtsiLowerMac:
                                       slot_flags=fl)
                 if lq is not None:
                     frames[-1].update(burst_quality(lq[0][ch, b]))
+                if tr is not None:
+                    frames[-1].update(traffic_keys(tr[0][ch, b], tr[1][ch, b], kind, bool(tr[2][ch])))
             out.append(frames)
         return out
 

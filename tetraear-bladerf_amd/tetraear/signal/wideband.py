@@ -232,7 +232,7 @@ class WidebandReceiver:
 
 
     def decode(self, x, cells, mac=False, timebase=False, tol=64, link_quality=False,
-               tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT):
+               tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False):
         """x [Nw] -> per carrier the frames decoded from it, each burst once (merge_chunks), in row
         order: demod, then the ETSI lower MAC on every (carrier, chunk) with carrier k's scrambling
         init cells[k].  A frame is the lower MAC's dict (core/etsi.py) plus "chunk" and "sample" (its
@@ -253,12 +253,17 @@ class WidebandReceiver:
         strongest soft bits) instead of the earlier row's.  tetra_etsi_link_quality runs first, on the
         intact rows, for the weights; its keys appear on the frames only with link_quality=True.
         ``slot_flags`` bit 2: the burst's own SYNC was outvoted.  ``tvote`` [M, 4] holds the last call's
-        ballots per carrier (cast, agreed, outvoted, won)."""
+        ballots per carrier (cast, agreed, outvoted, won).  traffic=True: every frame gains ``usage`` and
+        ``traffic`` as EtsiLowerMac(traffic=True)'s frames carry them, from one tetra_etsi_traffic call over
+        all (carrier, chunk) rows with G = chunks per carrier; with timebase=True or "vote" that call's
+        slots and keep are passed in (frame 18 reads "control", and a burst two chunks share is exported
+        from the copy kept)."""
         return self._decode(x, np.asarray(cells, np.uint32), None, mac, timebase, tol, link_quality=link_quality,
-                            tdma_cap=tdma_cap)[0]
+                            tdma_cap=tdma_cap, traffic=traffic)[0]
 
     def decode_acquire(self, x, cell_init, mac=False, timebase=False, tol=64, link_quality=False, score=None,
-                       vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT):
+                       vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT,
+                       traffic=False, acquired=None):
         """decode without given cells: cell_init [M] holds each carrier's scrambling init before the
         capture (3 = unknown); every carrier's cell comes from the last CRC-good BSCH over all of its
         chunk rows, and all of its rows are descrambled with it (tetra_lmac_etsi_acquire_groups, G =
@@ -268,25 +273,33 @@ class WidebandReceiver:
         score [M] int32 (C-contiguous, updated in place): the cell is chosen by the vote instead
         (tetra_lmac_etsi_vote_groups: every CRC-good BSCH weighed by its soft bits, cell_init[k] defending
         with score[k], scores bounded by vote_cap); at most 32 chunks per carrier.  The return is the same.
-        timebase="vote": decode's, the blocks scored with the cell acquired for the carrier."""
+        timebase="vote": decode's, the blocks scored with the cell acquired for the carrier.
+        traffic=True: decode's, every carrier's slots descrambled with the cell acquired for it; a carrier
+        without a cell -- no CRC-good BSCH in this capture, and none before it: acquired [M] bool, or by
+        default cell_init[k] == 3 -- reports ``usage`` None (its blocks were descrambled with no cell, so
+        a failed CRC says nothing).  The default misreads a carrier whose known cell is all zero (MCC =
+        MNC = colour code = 0), which has the init of "unknown": pass ``acquired`` for such a carrier, as
+        WidebandStream does from piece to piece."""
         state = np.array(cell_init, np.uint32)
         if state.shape != (self.plan.M,):
             raise ValueError(f"cell_init holds {state.shape} inits, the receiver has {self.plan.M} carriers")
         if score is not None and not (isinstance(score, np.ndarray) and score.dtype == np.int32 and
                                       score.shape == (self.plan.M,) and score.flags["C_CONTIGUOUS"]):
             raise ValueError(f"score must be a C-contiguous int32 array of {self.plan.M} (it is updated in place)")
+        had = state != 3 if acquired is None else np.asarray(acquired, bool)
         frames, ngood = self._decode(x, None, state, mac, timebase, tol, link_quality=link_quality, score=score,
-                                     vote_cap=vote_cap, tdma_cap=tdma_cap)
+                                     vote_cap=vote_cap, tdma_cap=tdma_cap, traffic=traffic, acquired=had)
         return frames, state, ngood
 
     def _decode(self, x, cells, state, mac, timebase=False, tol=64, tdma=None, advance=0, link_quality=False,
                 score=None, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_score=None,
-                tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT):
+                tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, acquired=None):
         """The chain behind decode (cells [M]) and decode_acquire (state [M], updated in place; score [M]
         int32 or None, likewise: the vote): (frames, ngood or None).  timebase: tdma [M] ETSI_TDMA (in/out; None: new streams), whose bit0
         moves on by ``advance`` bits after the call (WidebandStream).  timebase="vote": tdma_score [M] int32
-        (in/out; None: zeros) beside it, scores bounded by tdma_cap."""
-        from tetraear.core.etsi import EtsiLowerMac, run_link_quality
+        (in/out; None: zeros) beside it, scores bounded by tdma_cap.  traffic: tetra_etsi_traffic after
+        the MAC call; acquired [M] bool: the carriers that had a cell before the call (acquisition)."""
+        from tetraear.core.etsi import EtsiLowerMac, run_link_quality, run_traffic
         if timebase not in (False, True, "vote"):
             raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
         if timebase and (self.m2 % 2 or tol % 2 or tol < 0):
@@ -320,7 +333,7 @@ class WidebandReceiver:
                 c.check(c.lib.tetra_lmac_etsi_acquire_groups(c.handle, *rows, nchunk, _hip.ptr(state),
                                                              _hip.ptr(ngood), *outs),
                         "tetra_lmac_etsi_acquire_groups")
-        pdus = lq = None
+        pdus = lq = tr = None
         if link_quality or timebase == "vote":   # the rows are intact (origin 0); carrier k's rows with its (acquired) cell
             lq = run_link_quality(c, soft.reshape(C, -1), hard.reshape(C, -1), 0, nchunk,
                                   cells if state is None else state, nb, bursts, nk, blocks, t1)
@@ -345,6 +358,9 @@ class WidebandReceiver:
                                                     *outs[:4], _hip.ptr(t1), _hip.ptr(tdma), _hip.ptr(keep),
                                                     _hip.ptr(slots), _hip.ptr(npdu), _hip.ptr(recs)),
                         "tetra_etsi_mac_groups")
+            if traffic:
+                tr = run_traffic(c, soft.reshape(C, -1), 0, nchunk, cells if state is None else state, nb, bursts, nk,
+                                 blocks, slots, keep)
             keep = keep.astype(bool)
             pdus = (slots, npdu, recs)
         else:
@@ -352,7 +368,13 @@ class WidebandReceiver:
         if mac and not timebase:   # the PDU walk is per block; a fresh timebase per row, its slots not reported
             pdus = EtsiLowerMac(mac=True)._run_mac(c, C, np.ascontiguousarray(ns.reshape(-1)), nb, bursts, nk, blocks,
                                                   t1, None)
-        frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1, pdus, lq if link_quality else None)
+        if traffic:
+            if tr is None:
+                tr = run_traffic(c, soft.reshape(C, -1), 0, nchunk, cells if state is None else state, nb, bursts, nk,
+                                 blocks)
+            has = np.ones(M, bool) if state is None else (ngood > 0) | acquired
+            tr += (np.repeat(has, nchunk),)
+        frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1, pdus, lq if link_quality else None, tr)
         if mac and not timebase:
             for fr in frames:
                 for f in fr:
@@ -397,6 +419,8 @@ class WidebandStream:
     ``tdma_scores`` (reset() clears it); ``tdma_cap`` bounds it.  Within a buffer the best copy of a burst
     is kept; the choice between a burst's copies in two successive buffers stays "first decoded" (``last``).
     ``link_quality=True``: the frames and blocks carry the link-quality keys (WidebandReceiver.decode).
+    ``traffic=True``: the frames carry ``usage`` / ``traffic`` (WidebandReceiver.decode); in acquisition a
+    carrier reports ``usage`` None until a buffer holds its first CRC-good BSCH.
     ``vote=True`` (acquisition only): a carrier's cell is chosen by the vote over each buffer's BSCH
     blocks (WidebandReceiver.decode_acquire(score=...)), the score it gathers carried from piece to piece
     in ``cell_score`` and read as ``cell_scores`` (reset() clears it).  A burst in the carried tail is
@@ -410,9 +434,10 @@ class WidebandStream:
 
     def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False, timebase=False,
                  link_quality=False, vote=False, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT,
-                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT):
+                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False):
         if timebase not in (False, True, "vote"):
             raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
+        self.traffic = bool(traffic)
         self.rx = WidebandReceiver(fs, M, m2, oversample)
         self.acquire, self.mac, self.timebase = cells is None, bool(mac), bool(timebase)
         self.tdma_vote, self.tdma_cap = timebase == "vote", int(tdma_cap)
@@ -468,7 +493,8 @@ class WidebandStream:
             frames, ngood = self.rx._decode(buf, self._cells, state, True, "vote" if self.tdma_vote else True, 64,
                                             self.tdma, advance, link_quality=self.link_quality,
                                             score=self.cell_score, vote_cap=self.vote_cap,
-                                            tdma_score=self.tdma_score, tdma_cap=self.tdma_cap)
+                                            tdma_score=self.tdma_score, tdma_cap=self.tdma_cap, traffic=self.traffic,
+                                            acquired=self.acquired)
             if self.acquire:
                 self.cell_state = state
                 self.acquired |= ngood > 0
@@ -476,10 +502,14 @@ class WidebandStream:
         kw = {"mac": True} if self.mac else {}
         if self.link_quality:
             kw["link_quality"] = True
+        if self.traffic:
+            kw["traffic"] = True
         if not self.acquire:
             return self.rx.decode(buf, self._cells, **kw)
         if self.vote:
             kw.update(score=self.cell_score, vote_cap=self.vote_cap)
+        if self.traffic:
+            kw["acquired"] = self.acquired
         frames, self.cell_state, ngood = self.rx.decode_acquire(buf, self.cell_state, **kw)
         self.acquired |= ngood > 0
         return frames
