@@ -811,6 +811,120 @@ int tetra_etsi_traffic(tetra_ctx *ctx, const int8_t *softbits, size_t C, size_t 
                        const int32_t *slots /*[C][MAXB][4] or NULL*/, const int32_t *keep /*[C][MAXB] or NULL*/,
                        int32_t *tq /*[C][MAXB][4]*/, int8_t *tch /*[C][MAXB][432]*/);
 
+/* TM-SDUs and fragment reassembly (a new symbol of ABI version 2; nothing existing changed shape):
+ * where the TM-SDU of every recorded MAC-RESOURCE / MAC-FRAG / MAC-END PDU lies, its bytes, and the
+ * fragments of a carrier joined across bursts, chunks and overlapping rows into whole TM-SDUs -- what
+ * an upper MAC consumes (the reference's MacPDU.data / reassembled_data, protocol.py:560-596, which
+ * keeps one fragment buffer that every MAC-RESOURCE overwrites).  It runs after tetra_etsi_mac /
+ * _groups / _vote_groups on their npdu / pdus (and keep) and on the type1 rows they read.  All exact
+ * integers, restated in tests/_etsi_sdu_model.py.  The element layouts below are transcribed from EN
+ * 300 392-2 §21.4.3 / §21.5.2 and not pinned against a conformance vector; the
+ * records carry the raw fields, so a correction is a change to this table and the model's.
+ *
+ * Part A, per recorded PDU q < min(npdu[c][j], MAXPDU) of block j < nblock[c] (clamped) with crc_ok != 0
+ * and block kind SCH/F, SCH/HD or BSCH: sdu [C][MAXJ][MAXPDU][TETRA_SDU_FIELDS].  Records past that
+ * count, and records of blocks with npdu == 0, CRC-bad blocks and j >= nblock[c], are not written.
+ * With off = PDU OFFSET, end = off + PDU NBITS, the optional elements begin at off + HDR_BITS:
+ *   MAC-RESOURCE  power control flag 1 [+ power control 4]; slot granting flag 1 [+ slot granting 8];
+ *                 channel allocation flag 1 [+ body]
+ *   MAC-END       slot granting flag 1 [+ slot granting 8]; channel allocation flag 1 [+ body]
+ *   MAC-FRAG      none
+ *   channel allocation body: allocation type 2, timeslot assigned 4, up/downlink assigned 2, CLCH
+ *                 permission 1, cell change flag 1, carrier number 12, extended carrier numbering flag 1
+ *                 [+ band 4, offset 2, duplex spacing 3, reverse operation 1], monitoring pattern 2
+ *                 [+ frame-18 monitoring pattern 2 if monitoring pattern == 0]
+ * Up/downlink assigned == 0 is the augmented form: not walked, STATUS 4.  The TM-SDU runs from the end
+ * of the elements to end; with the fill-bit indication set, the last 1 bit before end (at or behind
+ * the elements' end) and the zeros after it are fill, and the SDU ends before that 1.  0 bits is valid.
+ *   STATUS       0 ok.  1 none: a kind without a TM-SDU (SYNC, broadcast, supplementary), a null PDU, or
+ *                PDU STATUS != 0.  2 malformed: an element runs past end, the fill flag is set and no 1
+ *                lies behind the elements, or the PDU record itself does not lie inside the block.  3
+ *                encrypted: a MAC-RESOURCE with ENC != 0; elements are not interpreted, the exported bits
+ *                are the PDU's from off + HDR_BITS to end, untouched.  4 unsupported.
+ *   OFFSET,NBITS first TM-SDU bit in the block and its length (0, 0 unless STATUS is 0 or 3)
+ *   BYTE         byte offset of this SDU in the block's sdu_data row (the running sum of the earlier
+ *                SDUs' (NBITS + 7) / 8; written for every record)
+ *   ROLE         by kind, whatever the status: 1 first fragment (MAC-RESOURCE with L == 63), 2 middle
+ *                (MAC-FRAG), 3 last (MAC-END), else 0 (whole, or none)
+ *   ELEMS        bit 0 power control present, bit 1 slot granting, bit 2 channel allocation, bit 3 the
+ *                extended carrier numbering fields
+ *   POWER_GRANT  power control | slot granting << 8 | the 10 extended carrier bits << 16
+ *   CHAN         the 10 bits allocation type .. cell change flag | frame-18 monitoring pattern << 10 |
+ *                carrier number << 16 | monitoring pattern << 28
+ *   A walk that stops (STATUS 2 or 4) keeps in ELEMS / POWER_GRANT / CHAN what it read before; a value
+ *   is read whole or not at all, and so are the ten bits allocation type .. cell change flag and the ten
+ *   extended carrier bits.
+ * sdu_data [C][MAXJ][TETRA_SDU_ROW]: the (NBITS + 7) / 8 bytes of every STATUS 0 / 3 SDU at BYTE, MSB
+ * first, the last byte zero-padded; bytes not covered by an SDU are not written.
+ *
+ * Part B, per group of G rows (tetra_etsi_mac_groups' grouping: row i of a group starts row_bits after
+ * row i - 1, the live bursts in the order (pos, row, b), pos = i row_bits + start bit): frag [C / G]
+ * (in/out; all zero = a new stream) joins the fragments.  keep [C][MAXB] NULL means every burst; where
+ * given, a burst with keep == 0 is skipped.  G == 1, row_bits == 0 and keep == NULL is the streaming form:
+ * bit0 advances by 2 max(nsym[c] - 1, 0) (nsym required); otherwise by `advance` (nsym not read).
+ * The walk visits the kept bursts in order, p = bit0 + pos; of each burst the blocks j ascending with
+ * blocks[c][j] burst index == b that Part A wrote records for; of each block its recorded PDUs in order.
+ * With, for a chain, d = p - last_bit, k = floor((d + 255) / 510):
+ *   1. Expiry.  Before each kept burst every active chain with k > gap_slots is freed, dropped += 1.
+ *   2. Same timeslot: k >= 0, k % 4 == 0 and |d - 510 k| <= TETRA_TDMA_TOL (k == 0: the same burst).
+ *   3. ROLE 1, STATUS 0: every active chain on the same timeslot is freed (superseded), dropped += 1
+ *      each; the lowest free chain is taken, else the chain with the smallest last_bit (the lowest index
+ *      among equals) is evicted, dropped += 1.  It starts with the SDU's bits: ssi / addr_type / aux /
+ *      enc of the PDU, nfrag = fed = 1, span = 0, last_bit = p.
+ *   4. ROLE 2 or 3, STATUS 0: the lowest active chain on the same timeslot takes the bits, appended at
+ *      its bit length; none: orphans += 1.  If nbits would exceed 8 TETRA_SDU_MAXBYTES the chain is freed,
+ *      dropped += 1, and nothing more happens.  Else nfrag += 1, span += k, fed += (k > 0), last_bit = p;
+ *      a ROLE 3 then writes a done record and frees the chain.
+ *   5. ROLE 1 with STATUS != 0 starts nothing; ROLE 2 / 3 with STATUS != 0 is an orphan.  ROLE 0: nothing.
+ *   6. After the walk bit0 advances.
+ * ndone [C / G] (fully written) counts the completions of the call; the first maxd are recorded in done
+ * [C / G][maxd][TETRA_DONE_FIELDS] with the (NBITS + 7) / 8 bytes in done_data [C / G][maxd]
+ * [TETRA_SDU_MAXBYTES]; the rest, and bytes past a message's, are not written (maxd == 0: done and
+ * done_data may be NULL).  ROW is the row c of the call, BURST / BLOCK (j) / PDU where the MAC-END sat;
+ * GAPS = SPAN / 4 + 1 - FED, the same-timeslot slots between the first and last feed that fed nothing:
+ * 0 means no fragment can have been lost.
+ *
+ * C == 0, a NULL required array, G outside 1..64, C % G != 0, row_bits, gap_slots or maxd < 0, C > 2^24:
+ * TETRA_E_INVALID, nothing written.  Host or device pointers; with device pointers the call enqueues two
+ * kernels on the context stream and returns without waiting. */
+#define TETRA_SDU_ROW 40            /* 268 bits plus at most 7 pad bits for each of 4 PDUs */
+#define TETRA_SDU_MAXBYTES 512      /* a chain's longest TM-SDU (unpinned: overflow drops the chain) */
+#define TETRA_FRAG_CHAINS 4         /* a carrier has four timeslots */
+enum {
+    TETRA_SDU_STATUS = 0, TETRA_SDU_OFFSET, TETRA_SDU_NBITS, TETRA_SDU_BYTE, TETRA_SDU_ROLE, TETRA_SDU_ELEMS,
+    TETRA_SDU_POWER_GRANT, TETRA_SDU_CHAN, TETRA_SDU_FIELDS = 8
+};
+enum { TETRA_SDU_OK = 0, TETRA_SDU_NONE, TETRA_SDU_MALFORMED, TETRA_SDU_ENCRYPTED, TETRA_SDU_UNSUPPORTED };
+enum { TETRA_ROLE_WHOLE = 0, TETRA_ROLE_FIRST, TETRA_ROLE_MIDDLE, TETRA_ROLE_LAST };
+enum {
+    TETRA_DONE_ROW = 0, TETRA_DONE_BURST, TETRA_DONE_BLOCK, TETRA_DONE_PDU, TETRA_DONE_SSI, TETRA_DONE_ADDR_TYPE,
+    TETRA_DONE_AUX, TETRA_DONE_ENC, TETRA_DONE_NBITS, TETRA_DONE_NFRAG, TETRA_DONE_SPAN, TETRA_DONE_FED,
+    TETRA_DONE_GAPS, TETRA_DONE_FIELDS = 13
+};
+typedef struct tetra_etsi_frag_chain {
+    int64_t last_bit;                  /* stream bit of the burst that fed it last */
+    int32_t active;
+    int32_t ssi, addr_type, aux, enc;  /* of the starting PDU */
+    int32_t nbits, nfrag;
+    int32_t span;                      /* slots from the first feed to the last */
+    int32_t fed;                       /* distinct bursts that fed it */
+    int32_t reserved;
+    uint8_t data[TETRA_SDU_MAXBYTES];  /* MSB first, zero behind nbits in its last byte */
+} tetra_etsi_frag_chain;
+typedef struct tetra_etsi_frag {       /* per carrier, carried from call to call; all zero = new stream */
+    int64_t bit0;                      /* stream bit index of this call's position 0 */
+    int32_t dropped;                   /* chains freed unfinished: expired, superseded, evicted, overflowed */
+    int32_t orphans;                   /* middle / last fragments that found no chain */
+    tetra_etsi_frag_chain chain[TETRA_FRAG_CHAINS];
+} tetra_etsi_frag;
+int tetra_etsi_sdu(tetra_ctx *ctx, const int32_t *nsym, size_t C, size_t G, int64_t row_bits, int64_t advance,
+                   int32_t gap_slots, const int32_t *nburst, const int32_t *bursts, const int32_t *nblock,
+                   const int32_t *blocks, const uint8_t *type1, const int32_t *npdu, const int32_t *pdus,
+                   const int32_t *keep /*[C][MAXB] or NULL*/, int32_t *sdu /*[C][MAXJ][MAXPDU][8]*/,
+                   uint8_t *sdu_data /*[C][MAXJ][40]*/, tetra_etsi_frag *frag /*[C/G] in/out*/, int32_t maxd,
+                   int32_t *ndone /*[C/G]*/, int32_t *done /*[C/G][maxd][13]*/,
+                   uint8_t *done_data /*[C/G][maxd][512]*/);
+
 /* The ETSI receiver's AFC mixer on a streaming window: out [C][N] cf32 = iq (cf32 rows ld samples
  * apart) x exp(-j 2 pi f (n0 + n) / fs), n0 = the window's first sample in the capture (frequency_shift's
  * float64 arithmetic, processor.py:85-100, with one continuous phase across windows); mix_c [C] as

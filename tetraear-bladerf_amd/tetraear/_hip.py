@@ -93,6 +93,19 @@ TV_BALLOTS, TV_AGREED, TV_OUTVOTED, TV_WON, TV_FIELDS = range(5)
 TQ_CLASS, TQ_NBITS, TQ_WSUM, TQ_NZERO, TQ_FIELDS = range(5)
 TCH_NONE, TCH_CONTROL, TCH_FULL, TCH_HALF, TCH_LOST = range(5)
 TCH_BITS = 432
+# tetra_etsi_sdu (include/tetra_hip.h): the TM-SDU records, the done records, struct tetra_etsi_frag
+SDU_ROW, SDU_MAXBYTES, FRAG_CHAINS = 40, 512, 4
+SDU_STATUS, SDU_OFFSET, SDU_NBITS, SDU_BYTE, SDU_ROLE, SDU_ELEMS, SDU_POWER_GRANT, SDU_CHAN, SDU_FIELDS = range(9)
+SDU_OK, SDU_NONE, SDU_MALFORMED, SDU_ENCRYPTED, SDU_UNSUPPORTED = range(5)
+ROLE_WHOLE, ROLE_FIRST, ROLE_MIDDLE, ROLE_LAST = range(4)
+(DONE_ROW, DONE_BURST, DONE_BLOCK, DONE_PDU, DONE_SSI, DONE_ADDR_TYPE, DONE_AUX, DONE_ENC, DONE_NBITS, DONE_NFRAG,
+ DONE_SPAN, DONE_FED, DONE_GAPS, DONE_FIELDS) = range(14)
+ETSI_FRAG_CHAIN = __import__("numpy").dtype([("last_bit", "<i8"), ("active", "<i4"), ("ssi", "<i4"), ("addr_type", "<i4"),
+                                            ("aux", "<i4"), ("enc", "<i4"), ("nbits", "<i4"), ("nfrag", "<i4"),
+                                            ("span", "<i4"), ("fed", "<i4"), ("reserved", "<i4"),
+                                            ("data", "u1", (SDU_MAXBYTES,))])
+ETSI_FRAG = __import__("numpy").dtype([("bit0", "<i8"), ("dropped", "<i4"), ("orphans", "<i4"),
+                                      ("chain", ETSI_FRAG_CHAIN, (FRAG_CHAINS,))])
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -175,6 +188,8 @@ def _bind(L):
                                            _vp]),
         "tetra_etsi_traffic": (_i32, [_vp, _vp, _sz, _sz, ctypes.c_int32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp]),
+        "tetra_etsi_sdu": (_i32, [_vp, _vp, _sz, _sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
         "tetra_etsi_mix": (_i32, [_vp, _vp, _sz, _sz, _sz, _vp, ctypes.c_double, ctypes.c_int64, _vp]),
         "tetra_etsi_decode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
         "tetra_etsi_encode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp]),

@@ -90,7 +90,7 @@ class TetraDecoder:
 
     def __init__(self, key_manager=None, auto_decrypt: bool = True, mode=None, mac: bool = False,
                  link_quality: bool = False, vote: bool = False, timebase_vote: bool = False,
-                 traffic: bool = False):
+                 traffic: bool = False, sdu: bool = False):
         self.SYNC_PATTERN = [0, 1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0,
                              1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0]
         self.FRAME_LENGTH = 510
@@ -109,6 +109,8 @@ class TetraDecoder:
         self.etsi_timebase_vote = bool(timebase_vote)
         # mode="etsi": every frame's usage and a traffic slot's descrambled soft bits (EtsiLowerMac(traffic=True))
         self.etsi_traffic = bool(traffic)
+        # mode="etsi", mac=True: TM-SDUs and joined fragments from the device records (EtsiLowerMac(sdu=True))
+        self.etsi_sdu = bool(sdu)
 
     # ------------------------------------------------------------------ keys and the reference's rest
     def set_keys(self, keys):
@@ -387,11 +389,15 @@ class TetraDecoder:
         rows, owner = [], []   # one row per CRC-good SCH/F / SCH/HD block, in order
         for i, f in enumerate(raw):
             for b in f["blocks"]:
-                if b["channel"] != "BSCH" and b["crc_ok"]:
+                if b["channel"] != "BSCH" and b["crc_ok"] and not self.etsi_sdu:
                     rows.append(np.asarray(b["bits"], np.uint8))
                     owner.append(i)
         fields, data = self.protocol_parser.mac_fields(rows) if rows else (None, None)
         pdus = [[] for _ in raw]
+        extra = [[] for _ in raw]   # sdu=True: sdu_bits and role of each MacPDU, for 'mac_pdus'
+        if self.etsi_sdu:
+            for i, f in enumerate(raw):
+                pdus[i], extra[i] = self._sdu_pdus(f)
         out = []
         k = 0
         for i, f in enumerate(raw):
@@ -424,12 +430,50 @@ class TetraDecoder:
             if frame:
                 frame['mac_pdus'] = [{'type': p.pdu_type.name, 'encrypted': p.encrypted, 'address': p.address,
                                       'length': p.length, 'data': p.data} for p in pdus[i]]
+                for d, x in zip(frame['mac_pdus'], extra[i]):
+                    d.update(x)
+                if "sdus" in f:
+                    frame['sdus'] = f["sdus"]
                 out.append(frame)
         return out
+
+    @staticmethod
+    def _sdu_pdus(f):
+        """sdu=True: the MacPDUs of one raw frame from the device records (tetra_etsi_mac's headers and
+        tetra_etsi_sdu's extents) instead of the raw-frame parser -- of every CRC-good SCH/F / SCH/HD
+        block, in block and PDU order, one per record but the null PDU.  pdu_type from the kind, encrypted
+        = encryption mode != 0, address = SSI, length = L, data = the TM-SDU bytes.  reassembled_data: on a
+        MAC-END that completed a chain the joined TM-SDU (the frame's ``sdus`` entry of its block and PDU), on a whole
+        MAC-RESOURCE with sdu_status 0 its own TM-SDU (as protocol.py:594 does), else empty.
+        Returns ([MacPDU], [dict(sdu_bits, role)])."""
+        from tetraear.core.protocol import MacPDU, PDUType
+        types = {"RESOURCE": PDUType.MAC_RESOURCE, "FRAG": PDUType.MAC_FRAG, "END": PDUType.MAC_END,
+                 "SYSINFO": PDUType.MAC_BROADCAST, "ACCESS-DEFINE": PDUType.MAC_BROADCAST,
+                 "BROADCAST": PDUType.MAC_BROADCAST, "SUPPLEMENTARY": PDUType.MAC_SUPPL}
+        joined = {(m.get("block", 0), m.get("pdu", 0)): m["data"] for m in f.get("sdus", ())}
+        out, extra = [], []
+        for b in f["blocks"]:
+            if b["channel"] == "BSCH" or not b["crc_ok"]:
+                continue
+            for q, p in enumerate(b.get("pdus", ())):
+                if p["kind"] not in types:
+                    continue
+                mode = p.get("encryption_mode", 0)
+                whole = b""
+                if p["kind"] == "END":   # a MAC-END that completed nothing (an orphan, an overflow) has no entry
+                    whole = joined.get((b["block"], q), b"")
+                elif p["kind"] == "RESOURCE" and p["role"] == 0 and p["sdu_status"] == 0:
+                    whole = p["sdu"]
+                out.append(MacPDU(pdu_type=types[p["kind"]], encrypted=mode != 0, address=p.get("ssi"),
+                                  length=p.get("length", 0), data=p["sdu"], fill_bits=p.get("fill", 0),
+                                  encryption_mode=mode, reassembled_data=whole))
+                extra.append({"sdu_bits": p["sdu_bits"], "role": p["role"]})
+        return out, extra
 
     def _etsi_rx(self):
         if self._etsi is None:
             from tetraear.core.etsi import EtsiLowerMac
             self._etsi = EtsiLowerMac(mac=self.etsi_mac, link_quality=self.etsi_link_quality, vote=self.etsi_vote,
-                                      timebase_vote=self.etsi_timebase_vote, traffic=self.etsi_traffic)
+                                      timebase_vote=self.etsi_timebase_vote, traffic=self.etsi_traffic,
+                                      sdu=self.etsi_sdu)
         return self._etsi

@@ -15,6 +15,9 @@ corrected.
 With ``traffic=True`` tetra_etsi_traffic (k_etsi_traffic) follows them: every burst gets a ``usage``, and
 a slot the control decoders could not read comes out as descrambled type-4 soft bits, which
 ``codec_frame`` lays out as the speech codec's input frame.
+With ``sdu=True`` (and ``mac=True``) tetra_etsi_sdu (k_sdu_walk, k_sdu_join) follows the MAC call: every PDU
+gets its TM-SDU, and a carrier's fragments are joined across bursts and calls; ``messages`` lists the
+finished TM-SDUs for an upper MAC.
 """
 import numpy as np
 
@@ -217,6 +220,88 @@ def slot_usage(frames):
     return out
 
 
+SDU_MAXD = 16   # done records a row (or a wideband carrier's group) can return from one call
+
+
+def run_sdu(c, nsym, G, row_bits, advance, nb, bursts, nk, blocks, t1, npdu, pdus, keep, frag, maxd=SDU_MAXD,
+            gap_slots=_hip.TDMA_EXPIRE):
+    """tetra_etsi_sdu on host arrays, frag [C / G] (_hip.ETSI_FRAG) updated in place: (sdu [C, MAXJ, MAXPDU,
+    8], sdu_data [C, MAXJ, 40], ndone [C / G], done [C / G, maxd, 13], done_data [C / G, maxd, 512])."""
+    C = len(nb)
+    sdu = np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.SDU_FIELDS), np.int32)
+    sdu_data = np.zeros((C, _hip.ETSI_MAXJ, _hip.SDU_ROW), np.uint8)
+    ndone = np.zeros(C // G, np.int32)
+    done = np.zeros((C // G, maxd, _hip.DONE_FIELDS), np.int32)
+    done_data = np.zeros((C // G, maxd, _hip.SDU_MAXBYTES), np.uint8)
+    c.check(c.lib.tetra_etsi_sdu(c.handle, _hip.ptr(nsym), C, G, row_bits, advance, gap_slots, _hip.ptr(nb),
+                                 _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1), _hip.ptr(npdu),
+                                 _hip.ptr(pdus), _hip.ptr(keep), _hip.ptr(sdu), _hip.ptr(sdu_data), _hip.ptr(frag), maxd,
+                                 _hip.ptr(ndone), _hip.ptr(done), _hip.ptr(done_data)), "tetra_etsi_sdu")
+    return sdu, sdu_data, ndone, done, done_data
+
+
+def sdu_keys(rec, row):
+    """One tetra_etsi_sdu record and its block's sdu_data row as the keys a pdu dict gains: ``sdu`` (the
+    TM-SDU's bytes, MSB first, zero-padded; empty unless sdu_status is 0 or 3), ``sdu_bits``,
+    ``sdu_status`` (0 ok, 1 none, 2 malformed, 3 encrypted, 4 unsupported), ``role`` (0 whole, 1 first, 2
+    middle, 3 last fragment) and, where present, ``power_control``, ``slot_granting`` and
+    ``channel_allocation`` (a dict of the raw fields)."""
+    r = [int(v) for v in rec]
+    n, at = r[_hip.SDU_NBITS], r[_hip.SDU_BYTE]
+    d = {"sdu": bytes(row[at:at + (n + 7) // 8]), "sdu_bits": n, "sdu_status": r[_hip.SDU_STATUS],
+         "role": r[_hip.SDU_ROLE]}
+    el, pg, ch = r[_hip.SDU_ELEMS], r[_hip.SDU_POWER_GRANT], r[_hip.SDU_CHAN]
+    if el & 1:
+        d["power_control"] = pg & 15
+    if el & 2:
+        d["slot_granting"] = (pg >> 8) & 255
+    if el & 4:
+        ca = {"allocation_type": (ch >> 8) & 3, "timeslot_assigned": (ch >> 4) & 15, "updownlink_assigned": (ch >> 2) & 3,
+              "clch_permission": (ch >> 1) & 1, "cell_change": ch & 1}
+        if r[_hip.SDU_STATUS] != _hip.SDU_UNSUPPORTED:   # the augmented form stops after these
+            ca.update(carrier=(ch >> 16) & 0xFFF, monitoring_pattern=(ch >> 28) & 3)
+            if ca["monitoring_pattern"] == 0:
+                ca["frame18_monitoring"] = (ch >> 10) & 3
+            if el & 8:
+                x = (pg >> 16) & 0x3FF
+                ca["extended"] = {"band": x >> 6, "offset": (x >> 4) & 3, "duplex_spacing": (x >> 1) & 7,
+                                  "reverse_operation": x & 1}
+        d["channel_allocation"] = ca
+    return d
+
+
+def done_dict(rec, data, block):
+    """One done record of tetra_etsi_sdu and its bytes as an entry of a frame's ``sdus``; ``block`` (the
+    block's index in its burst) and ``pdu`` say where the MAC-END sat."""
+    r = [int(v) for v in rec]
+    n = r[_hip.DONE_NBITS]
+    return {"ssi": None if r[_hip.DONE_SSI] < 0 else r[_hip.DONE_SSI], "address_type": r[_hip.DONE_ADDR_TYPE],
+            "aux": None if r[_hip.DONE_AUX] < 0 else r[_hip.DONE_AUX], "enc": r[_hip.DONE_ENC], "nbits": n,
+            "data": bytes(data[:(n + 7) // 8]), "fragments": r[_hip.DONE_NFRAG], "span_slots": r[_hip.DONE_SPAN],
+            "gaps": r[_hip.DONE_GAPS], "block": block, "pdu": r[_hip.DONE_PDU]}
+
+
+def messages(frames):
+    """One carrier's frames (sdu=True) -> its finished TM-SDUs in time order, what a caller hands to an
+    upper MAC: of every frame the whole ones -- a MAC-RESOURCE that is no fragment, with a TM-SDU of at
+    least one bit, sdu_status 0 or 3 (encrypted: ``enc`` != 0, the bits untouched) -- in block and PDU order,
+    then the ones a MAC-END of the frame completed (``sdus``).  Each is a dict(ssi, address_type, aux, enc,
+    nbits, data, fragments, span_slots, gaps, position[, tn, fn, mn]); a whole one has fragments 1, gaps 0."""
+    out = []
+    for f in frames:
+        where = {k: f[k] for k in ("position", "tn", "fn", "mn") if k in f}
+        for b in f["blocks"]:
+            for p in b.get("pdus", ()) if b["crc_ok"] else ():
+                if p["kind"] == "RESOURCE" and p.get("role") == _hip.ROLE_WHOLE and p["sdu_bits"] > 0 and \
+                        p["sdu_status"] in (_hip.SDU_OK, _hip.SDU_ENCRYPTED):
+                    out.append(dict(ssi=p["ssi"], address_type=p["address_type"], aux=p["aux"],
+                                    enc=p["encryption_mode"], nbits=p["sdu_bits"], data=p["sdu"], fragments=1,
+                                    span_slots=0, gaps=0, **where))
+        for m in f.get("sdus", ()):
+            out.append(dict(m, **where))
+    return out
+
+
 class EtsiLowerMac:
     """Lower MAC of the ETSI chain.  With a cell (mcc, mnc, colour_code) every channel is
     descrambled with it.  Without one the receiver acquires the cell itself: each chunk's BSCH
@@ -265,12 +350,23 @@ class EtsiLowerMac:
     such a slot is a candidate: a control burst lost to noise looks the same, and ``soft_sum`` and the
     timebase are what a caller gates on.  In acquisition mode a channel without a cell yet reports
     ``usage`` None.  decode_stream alternates two sets of rows as with ``link_quality=True``.  Everything
-    else in the frames is unchanged."""
+    else in the frames is unchanged.
+
+    ``sdu=True`` (with ``mac=True``): tetra_etsi_sdu runs after the MAC call.  Every pdu dict gains ``sdu``,
+    ``sdu_bits``, ``sdu_status``, ``role`` and the optional elements it carries (sdu_keys); a frame whose
+    burst held a MAC-END that completed a chain of fragments gains ``sdus``, a list of dict(ssi,
+    address_type, aux, enc, nbits, data, fragments, span_slots, gaps).  The fragment state is carried like
+    the timebase: per channel by decode_stream / decode, cleared by reset_stream(), fresh for every
+    decode_batch; ``frag_stats`` counts the chains dropped unfinished and the fragments that found no
+    chain.  ``messages(frames)`` lists a carrier's finished TM-SDUs.  Everything else is unchanged."""
 
     def __init__(self, mcc=None, mnc=None, colour_code=None, mac=False, link_quality=False, vote=False,
                  vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, timebase_vote=False,
-                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False):
+                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False):
         self.mac = bool(mac)
+        self.sdu = bool(sdu)
+        if self.sdu and not self.mac:
+            raise ValueError("sdu=True reads the PDU records of mac=True")
         self.traffic = bool(traffic)
         self.link_quality = bool(link_quality)
         self.timebase_vote, self.tdma_cap = bool(timebase_vote), int(tdma_cap)
@@ -300,6 +396,33 @@ class EtsiLowerMac:
         self._tdma = None   # [C] tetra_etsi_tdma: the carried timebases (mac=True)
         self.tdma_score = None   # [C] int32: the score each timebase has gathered (timebase_vote=True)
         self.cell_score = None   # vote=True: the cells start without incumbency (cell_state is kept)
+        self._frag = None   # [C] tetra_etsi_frag: the carried fragment chains (sdu=True)
+        self._frag_last = None   # the state the last call left (decode_batch's is not carried)
+        self._lost = None   # [C] completions beyond SDU_MAXD a call, which no frame carries
+
+    @property
+    def frag_stats(self):
+        """sdu=True: dict(dropped [C], orphans [C]) -- chains freed unfinished (expired, superseded,
+        evicted, overflowed) and middle / last fragments that found no chain -- since the stream began
+        (decode_batch: of that call); ``lost`` [C] counts the messages completed beyond the SDU_MAXD a call can
+        return per channel, which reach no frame; None before the first call."""
+        if self._frag_last is None:
+            return None
+        return {"dropped": self._frag_last["dropped"].copy(), "orphans": self._frag_last["orphans"].copy(),
+                "lost": self._lost.copy()}
+
+    def _run_sdu(self, c, nsym, nb, bursts, nk, blocks, t1, mac, frag):
+        """tetra_etsi_sdu in its streaming form on the MAC call's records (sdu=True; else None)."""
+        if not self.sdu:
+            return None
+        if frag is None or self._lost is None or len(self._lost) != len(nb):
+            self._lost = np.zeros(len(nb), np.int64)
+        if frag is None:
+            frag = np.zeros(len(nb), _hip.ETSI_FRAG)
+        self._frag_last = frag
+        sd = run_sdu(c, nsym, 1, 0, 0, nb, bursts, nk, blocks, t1, mac[1], mac[2], None, frag)
+        self._lost += np.maximum(sd[2] - SDU_MAXD, 0)
+        return sd
 
     @property
     def cells(self):
@@ -367,7 +490,8 @@ class EtsiLowerMac:
         lq = self._run_quality(c, soft, hard, 0, used, nb, bursts, nk, blocks, t1)
         mac = self._run_mac(c, C, nsym, nb, bursts, nk, blocks, t1, None, lq)
         tr = self._run_traffic(c, soft, 0, used, nb, bursts, nk, blocks, mac, used is self.cell_state)
-        return self._frames(C, nb, bursts, nk, blocks, t1, mac, lq if self.link_quality else None, tr)
+        sd = self._run_sdu(c, nsym, nb, bursts, nk, blocks, t1, mac, None)
+        return self._frames(C, nb, bursts, nk, blocks, t1, mac, lq if self.link_quality else None, tr, sd)
 
     def _score(self, C):
         """cell_score for C channels (vote=True): zeros when new or of another length."""
@@ -507,12 +631,16 @@ class EtsiLowerMac:
             self.tdma_score = np.zeros(C, np.int32)
         mac = self._run_mac(_hip.ctx(), C, nsym, nb, bursts, nk, blocks, t1, self._tdma, lq, self.tdma_score)
         tr = self._run_traffic(_hip.ctx(), srow, 2 * R, used, nb, bursts, nk, blocks, mac, used is self.cell_state)
-        return self._frames(C, nb, bursts, nk, blocks, t1, mac, lq if self.link_quality else None, tr)
+        if self.sdu and (self._frag is None or len(self._frag) != C):
+            self._frag = np.zeros(C, _hip.ETSI_FRAG)
+        sd = self._run_sdu(_hip.ctx(), nsym, nb, bursts, nk, blocks, t1, mac, self._frag)
+        return self._frames(C, nb, bursts, nk, blocks, t1, mac, lq if self.link_quality else None, tr, sd)
 
     @staticmethod
-    def _frames(C, nb, bursts, nk, blocks, t1, mac=None, lq=None, tr=None):
+    def _frames(C, nb, bursts, nk, blocks, t1, mac=None, lq=None, tr=None, sd=None, G=1):
         """mac: None, or tetra_etsi_mac's (slots, npdu, pdus) for the same call; lq: None, or
-        tetra_etsi_link_quality's (bq, kq); tr: None, or tetra_etsi_traffic's (tq, tch, has_cell [C])."""
+        tetra_etsi_link_quality's (bq, kq); tr: None, or tetra_etsi_traffic's (tq, tch, has_cell [C]); sd:
+        None, or tetra_etsi_sdu's (sdu, sdu_data, ndone, done, done_data) over groups of G rows."""
         out = []
         for ch in range(C):
             frames = []
@@ -528,6 +656,9 @@ class EtsiLowerMac:
                     if mac is not None:
                         n = int(mac[1][ch, j])
                         blks[-1].update(npdu=n, pdus=[pdu_dict(r) for r in mac[2][ch, j, :min(n, _hip.ETSI_MAXPDU)]])
+                        if sd is not None:
+                            for q, p in enumerate(blks[-1]["pdus"]):
+                                p.update(sdu_keys(sd[0][ch, j, q], sd[1][ch, j]))
                     if lq is not None:
                         blks[-1].update(block_quality(lq[1][ch, j], k))
                 frames.append({"position": start, "burst": BURST_NAMES[kind], "burst_kind": kind,
@@ -543,6 +674,12 @@ class EtsiLowerMac:
                 if tr is not None:
                     frames[-1].update(traffic_keys(tr[0][ch, b], tr[1][ch, b], kind, bool(tr[2][ch])))
             out.append(frames)
+        if sd is not None:   # a finished chain goes to the frame of the burst that held its MAC-END
+            for g in range(C // G):
+                for i in range(min(int(sd[2][g]), sd[3].shape[1])):
+                    row, b = int(sd[3][g, i, _hip.DONE_ROW]), int(sd[3][g, i, _hip.DONE_BURST])
+                    blk = int(blocks[row, int(sd[3][g, i, _hip.DONE_BLOCK]), 3])
+                    out[row][b].setdefault("sdus", []).append(done_dict(sd[3][g, i], sd[4][g, i], blk))
         return out
 
     def decode(self, symbols, soft_bits=None, stream=True):

@@ -170,6 +170,7 @@ class WidebandReceiver:
         self.etsi = etsi_plan(2.4e6)   # timing-loop constants (the channel-filter taps are not used)
         self.m2 = m2
         self.tvote = None   # [M, 4] int32: the ballots of the last decode with timebase="vote"
+        self.frag_stats = None   # dict(dropped [M], orphans [M]) of the last decode with sdu=True
 
     def channelize(self, x, n_keep=None):
         """x [Nw] complex64 or [Nw, 2] int16 -> y [M][n_keep] complex64 at 72 kHz."""
@@ -232,7 +233,7 @@ class WidebandReceiver:
 
 
     def decode(self, x, cells, mac=False, timebase=False, tol=64, link_quality=False,
-               tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False):
+               tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False):
         """x [Nw] -> per carrier the frames decoded from it, each burst once (merge_chunks), in row
         order: demod, then the ETSI lower MAC on every (carrier, chunk) with carrier k's scrambling
         init cells[k].  A frame is the lower MAC's dict (core/etsi.py) plus "chunk" and "sample" (its
@@ -257,13 +258,19 @@ class WidebandReceiver:
         ``traffic`` as EtsiLowerMac(traffic=True)'s frames carry them, from one tetra_etsi_traffic call over
         all (carrier, chunk) rows with G = chunks per carrier; with timebase=True or "vote" that call's
         slots and keep are passed in (frame 18 reads "control", and a burst two chunks share is exported
-        from the copy kept)."""
+        from the copy kept).  sdu=True (needs mac=True and timebase=True or "vote", else ValueError): one
+        tetra_etsi_sdu call over all rows with G = chunks per carrier and the MAC call's keep, a new stream
+        per call: every pdu dict gains ``sdu`` / ``sdu_bits`` / ``sdu_status`` / ``role`` and its optional
+        elements, and the frame whose MAC-END completed a chain of fragments gains ``sdus``, as
+        EtsiLowerMac(sdu=True)'s frames carry them (core/etsi.py messages() lists a carrier's finished
+        TM-SDUs); ``frag_stats`` holds the call's dropped / orphans per carrier and ``lost``, the messages
+        completed beyond the SDU_MAXD (core/etsi.py) a call returns per carrier, which reach no frame."""
         return self._decode(x, np.asarray(cells, np.uint32), None, mac, timebase, tol, link_quality=link_quality,
-                            tdma_cap=tdma_cap, traffic=traffic)[0]
+                            tdma_cap=tdma_cap, traffic=traffic, sdu=sdu)[0]
 
     def decode_acquire(self, x, cell_init, mac=False, timebase=False, tol=64, link_quality=False, score=None,
                        vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT,
-                       traffic=False, acquired=None):
+                       traffic=False, acquired=None, sdu=False):
         """decode without given cells: cell_init [M] holds each carrier's scrambling init before the
         capture (3 = unknown); every carrier's cell comes from the last CRC-good BSCH over all of its
         chunk rows, and all of its rows are descrambled with it (tetra_lmac_etsi_acquire_groups, G =
@@ -279,7 +286,7 @@ class WidebandReceiver:
         default cell_init[k] == 3 -- reports ``usage`` None (its blocks were descrambled with no cell, so
         a failed CRC says nothing).  The default misreads a carrier whose known cell is all zero (MCC =
         MNC = colour code = 0), which has the init of "unknown": pass ``acquired`` for such a carrier, as
-        WidebandStream does from piece to piece."""
+        WidebandStream does from piece to piece.  sdu=True: decode's."""
         state = np.array(cell_init, np.uint32)
         if state.shape != (self.plan.M,):
             raise ValueError(f"cell_init holds {state.shape} inits, the receiver has {self.plan.M} carriers")
@@ -288,20 +295,26 @@ class WidebandReceiver:
             raise ValueError(f"score must be a C-contiguous int32 array of {self.plan.M} (it is updated in place)")
         had = state != 3 if acquired is None else np.asarray(acquired, bool)
         frames, ngood = self._decode(x, None, state, mac, timebase, tol, link_quality=link_quality, score=score,
-                                     vote_cap=vote_cap, tdma_cap=tdma_cap, traffic=traffic, acquired=had)
+                                     vote_cap=vote_cap, tdma_cap=tdma_cap, traffic=traffic, acquired=had, sdu=sdu)
         return frames, state, ngood
 
     def _decode(self, x, cells, state, mac, timebase=False, tol=64, tdma=None, advance=0, link_quality=False,
                 score=None, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_score=None,
-                tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, acquired=None):
+                tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, acquired=None, sdu=False, frag=None,
+                walked=None):
         """The chain behind decode (cells [M]) and decode_acquire (state [M], updated in place; score [M]
         int32 or None, likewise: the vote): (frames, ngood or None).  timebase: tdma [M] ETSI_TDMA (in/out; None: new streams), whose bit0
         moves on by ``advance`` bits after the call (WidebandStream).  timebase="vote": tdma_score [M] int32
         (in/out; None: zeros) beside it, scores bounded by tdma_cap.  traffic: tetra_etsi_traffic after
-        the MAC call; acquired [M] bool: the carriers that had a cell before the call (acquisition)."""
-        from tetraear.core.etsi import EtsiLowerMac, run_link_quality, run_traffic
+        the MAC call; acquired [M] bool: the carriers that had a cell before the call (acquisition).
+        sdu: tetra_etsi_sdu after the MAC call with its keep; frag [M] ETSI_FRAG (in/out; None: new
+        streams), whose bit0 moves on by ``advance`` too; walked [M] (72 kHz samples of this buffer, or
+        None): a carrier's bursts up to there were walked from the previous buffer and feed nothing now."""
+        from tetraear.core.etsi import EtsiLowerMac, run_link_quality, run_sdu, run_traffic
         if timebase not in (False, True, "vote"):
             raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
+        if sdu and not (mac and timebase):
+            raise ValueError("sdu=True reads the PDU records of mac=True and the keep of timebase=True or 'vote'")
         if timebase and (self.m2 % 2 or tol % 2 or tol < 0):
             raise ValueError(f"timebase=True works in bits: m2 ({self.m2}) and tol ({tol}) must be even")
         if timebase == "vote" and int(tdma_cap) <= 0:
@@ -333,7 +346,7 @@ class WidebandReceiver:
                 c.check(c.lib.tetra_lmac_etsi_acquire_groups(c.handle, *rows, nchunk, _hip.ptr(state),
                                                              _hip.ptr(ngood), *outs),
                         "tetra_lmac_etsi_acquire_groups")
-        pdus = lq = tr = None
+        pdus = lq = tr = sd = None
         if link_quality or timebase == "vote":   # the rows are intact (origin 0); carrier k's rows with its (acquired) cell
             lq = run_link_quality(c, soft.reshape(C, -1), hard.reshape(C, -1), 0, nchunk,
                                   cells if state is None else state, nb, bursts, nk, blocks, t1)
@@ -361,6 +374,15 @@ class WidebandReceiver:
             if traffic:
                 tr = run_traffic(c, soft.reshape(C, -1), 0, nchunk, cells if state is None else state, nb, bursts, nk,
                                  blocks, slots, keep)
+            if sdu:
+                fed = keep
+                if walked is not None:   # the carried tail's bursts were walked from the previous buffer
+                    sample = (np.arange(C) % nchunk)[:, None] * self.m2 + 2 * bursts[:, :, 0]
+                    fed = np.ascontiguousarray(keep * (sample > np.repeat(walked, nchunk)[:, None]), np.int32)
+                frag = np.zeros(M, _hip.ETSI_FRAG) if frag is None else frag
+                sd = run_sdu(c, None, nchunk, self.m2 // 2, advance, nb, bursts, nk, blocks, t1, npdu, recs, fed, frag)
+                self.frag_stats = {"dropped": frag["dropped"].copy(), "orphans": frag["orphans"].copy(),
+                                   "lost": np.maximum(sd[2].astype(np.int64) - sd[3].shape[1], 0)}
             keep = keep.astype(bool)
             pdus = (slots, npdu, recs)
         else:
@@ -374,7 +396,7 @@ class WidebandReceiver:
                                  blocks)
             has = np.ones(M, bool) if state is None else (ngood > 0) | acquired
             tr += (np.repeat(has, nchunk),)
-        frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1, pdus, lq if link_quality else None, tr)
+        frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1, pdus, lq if link_quality else None, tr, sd, nchunk)
         if mac and not timebase:
             for fr in frames:
                 for f in fr:
@@ -421,6 +443,11 @@ class WidebandStream:
     ``link_quality=True``: the frames and blocks carry the link-quality keys (WidebandReceiver.decode).
     ``traffic=True``: the frames carry ``usage`` / ``traffic`` (WidebandReceiver.decode); in acquisition a
     carrier reports ``usage`` None until a buffer holds its first CRC-good BSCH.
+    ``sdu=True`` (with ``mac=True`` and a timebase): the pdu dicts carry their TM-SDU and a frame whose
+    MAC-END completed a chain carries ``sdus`` (WidebandReceiver.decode); one fragment state per carrier
+    is carried from piece to piece in ``frag`` [M] with the advance of ``tdma`` (reset() clears it), and
+    the carried tail's bursts, decoded again, feed nothing a second time.  ``frag_stats``: the chains
+    dropped and the orphans per carrier since reset().
     ``vote=True`` (acquisition only): a carrier's cell is chosen by the vote over each buffer's BSCH
     blocks (WidebandReceiver.decode_acquire(score=...)), the score it gathers carried from piece to piece
     in ``cell_score`` and read as ``cell_scores`` (reset() clears it).  A burst in the carried tail is
@@ -434,10 +461,13 @@ class WidebandStream:
 
     def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False, timebase=False,
                  link_quality=False, vote=False, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT,
-                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False):
+                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False):
         if timebase not in (False, True, "vote"):
             raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
         self.traffic = bool(traffic)
+        self.sdu = bool(sdu)
+        if self.sdu and not (mac and timebase):
+            raise ValueError("sdu=True reads the PDU records of mac=True and the keep of timebase=True or 'vote'")
         self.rx = WidebandReceiver(fs, M, m2, oversample)
         self.acquire, self.mac, self.timebase = cells is None, bool(mac), bool(timebase)
         self.tdma_vote, self.tdma_cap = timebase == "vote", int(tdma_cap)
@@ -486,6 +516,15 @@ class WidebandStream:
         # timebase: each carrier's tetra_etsi_tdma; bit0 = the stream bit of the buffer's first output
         self.tdma = np.zeros(self.M, _hip.ETSI_TDMA) if self.timebase else None
         self.tdma_score = np.zeros(self.M, np.int32) if self.tdma_vote else None   # timebase="vote"
+        self.frag = np.zeros(self.M, _hip.ETSI_FRAG) if self.sdu else None   # sdu=True: the fragment chains
+        self.lost_sdus = np.zeros(self.M, np.int64)
+
+    @property
+    def frag_stats(self):
+        """sdu=True: dict(dropped [M], orphans [M], lost [M]: completions beyond a buffer's SDU_MAXD per
+        carrier, which reach no frame) since reset(); else None."""
+        return None if self.frag is None else {"dropped": self.frag["dropped"].copy(),
+                                               "orphans": self.frag["orphans"].copy(), "lost": self.lost_sdus.copy()}
 
     def _decode_buffer(self, buf, advance=0):
         if self.timebase:
@@ -494,10 +533,13 @@ class WidebandStream:
                                             self.tdma, advance, link_quality=self.link_quality,
                                             score=self.cell_score, vote_cap=self.vote_cap,
                                             tdma_score=self.tdma_score, tdma_cap=self.tdma_cap, traffic=self.traffic,
-                                            acquired=self.acquired)
+                                            acquired=self.acquired, sdu=self.sdu, frag=self.frag,
+                                            walked=self.last - self.y0 + self.tol if self.sdu else None)
             if self.acquire:
                 self.cell_state = state
                 self.acquired |= ngood > 0
+            if self.sdu:
+                self.lost_sdus += self.rx.frag_stats["lost"]
             return frames
         kw = {"mac": True} if self.mac else {}
         if self.link_quality:
@@ -529,6 +571,8 @@ class WidebandStream:
         assert not self.timebase or dy % 2 == 0, "a buffer starts a whole number of bits after the previous one"
         if n72 < 16 and self.timebase:   # (nothing decoded: no burst, no expiry, the scores stay)
             self.tdma["bit0"] += dy // 2
+            if self.sdu:
+                self.frag["bit0"] += dy // 2
         if n72 >= 16:
             for k, fr in enumerate(self._decode_buffer(buf, dy // 2)):
                 for f in fr:
