@@ -925,6 +925,75 @@ int tetra_etsi_sdu(tetra_ctx *ctx, const int32_t *nsym, size_t C, size_t G, int6
                    int32_t *ndone /*[C/G]*/, int32_t *done /*[C/G][maxd][13]*/,
                    uint8_t *done_data /*[C/G][maxd][512]*/);
 
+/* LLC headers, the frame check sequence and TL-SDUs (a new symbol of ABI version 2; nothing existing
+ * changed shape): a TM-SDU is an LLC PDU -- a 4-bit type, the basic link's sequence bits, the TL-SDU and,
+ * for half the types, a 32-bit FCS, the only end-to-end check a reassembled message has.  The call runs
+ * after tetra_etsi_sdu on that call's outputs (nblock / blocks / npdu / pdus as given to it; sdu, sdu_data,
+ * ndone, done, done_data as it left them) and writes one record per TM-SDU plus the TL-SDU byte-aligned.
+ * All exact integers, restated in tests/_etsi_llc_model.py.
+ *
+ * Pinned: the CRC arithmetic below (b"123456789" gives 0xFC891918; the register run on over a message's
+ * own FCS leaves 0xC704DD7B; for whole bytes the value is bitrev32(zlib.crc32(bytes(bitrev8(x) for x in
+ * data)))).  Transcribed from EN 300 392-2 §21.2 and NOT pinned against a conformance vector (DESIGN.md
+ * §5.25): that the FCS covers the LLC header, that it is sent most significant bit first, and the type
+ * table.  FCS_RX and FCS_CALC are both recorded, so another convention can be tried on recorded data.
+ *
+ * Part A, llc [C][MAXJ][MAXPDU][TETRA_LLC_FIELDS] and tl [C][MAXJ][TETRA_SDU_ROW]: one record for every
+ * record tetra_etsi_sdu's Part A writes (q < min(npdu[c][j], MAXPDU), j < nblock[c] clamped, crc_ok != 0,
+ * block kind SCH/F, SCH/HD or BSCH); the rest is not written.  Part B, llc_done [C / G][maxd]
+ * [TETRA_LLC_FIELDS] and tl_done [C / G][maxd][TETRA_SDU_MAXBYTES]: one record for each of the first
+ * min(max(ndone[g], 0), maxd) done records of a group; the rest is not written (maxd == 0: done,
+ * done_data, llc_done and tl_done may be NULL).
+ *
+ * The PDU's bits are the SDU's bytes from their first byte (sdu_data at BYTE, n = SDU NBITS bits; done_data,
+ * n = DONE NBITS), MSB first.  STATUS, the first rule that holds:
+ *   Part A  1 none       PDU KIND is not MAC-RESOURCE, or SDU ROLE != 0
+ *           3 encrypted  SDU STATUS == 3 or PDU ENC != 0: nothing read, TYPE -1
+ *           1 none       SDU STATUS 1, 2 or 4, or n <= 0
+ *           2 malformed  BYTE < 0 or BYTE + (n + 7) / 8 > TETRA_SDU_ROW (no record of tetra_etsi_sdu's):
+ *                        nothing read
+ *   Part B  3 encrypted  DONE ENC != 0: nothing read, TYPE -1
+ *           2 malformed  n < 0 or n > 8 TETRA_SDU_MAXBYTES: nothing read
+ *           1 none       n == 0
+ *   both    2 malformed  n < 4, or n < the type's header bits, plus 32 for a type with FCS
+ *           4 unsupported  TYPE 8..15 (the advanced link, supplementary, layer-2 signalling): TYPE is
+ *                        written, nothing else read
+ *           0 ok
+ *   TYPE      the first 4 bits: 0 BL-ADATA, 1 BL-DATA, 2 BL-UDATA, 3 BL-ACK, 4..7 the same four with FCS,
+ *             8 AL-SETUP, 9 AL-DATA / AL-FINAL, 10 AL-UDATA / AL-UFINAL, 11 AL-ACK / AL-RNR, 12 AL-RECONNECT,
+ *             13 supplementary, 14 layer-2 signalling, 15 AL-DISC
+ *   NR, NS    the basic link's one-bit sequence numbers behind TYPE, -1 where the type has none: BL-ADATA
+ *             N(R) then N(S) (header 6 bits), BL-DATA N(S) (5), BL-ACK N(R) (5), BL-UDATA neither (4)
+ *   OFFSET    first TL-SDU bit in the SDU: the header's length, 4, 5 or 6
+ *   NBITS     the TL-SDU's bits, n - OFFSET, less 32 for a type with FCS; 0 is valid (a bare BL-ACK)
+ *   HEAD      the first min(NBITS, 8) bits of the TL-SDU left-aligned in 8 bits, -1 when NBITS < 3;
+ *             HEAD >> 5 is the MLE protocol discriminator.  The device names nothing further.
+ *   FCS       0 the type has none (FCS_RX and FCS_CALC then read 0), 1 good, 2 bad
+ *   FCS_RX    the last 32 bits of the SDU, the first on air as bit 31 (the int32 holds the bit pattern)
+ *   FCS_CALC  with r = 0xFFFFFFFF and, for each bit b of the PDU in front of the FCS, header included, in
+ *             air order, t = (r >> 31) ^ b; r <<= 1; if (t) r ^= 0x04C11DB7: FCS_CALC = ~r.  Good iff
+ *             FCS_CALC == FCS_RX.
+ * With STATUS 1, 2, 3 or 4 every field not named in its row reads 0 (TYPE too on 1 and 2), NR and NS -1.
+ * tl / tl_done: of every STATUS 0 record the (NBITS + 7) / 8 bytes of the TL-SDU, MSB first, the last byte
+ * zero-padded -- in tl at the SDU's own BYTE offset in the block's row, in tl_done from byte 0; bytes not
+ * covered are not written.
+ *
+ * C == 0, a NULL required array, G outside 1..64, C % G != 0, maxd < 0, C > 2^24: TETRA_E_INVALID, nothing
+ * written.  Host or device pointers; with device pointers the call enqueues two kernels (one when maxd ==
+ * 0) on the context stream and returns without waiting (no allocation, no synchronising copy). */
+enum {
+    TETRA_LLC_STATUS = 0, TETRA_LLC_TYPE, TETRA_LLC_NR, TETRA_LLC_NS, TETRA_LLC_OFFSET, TETRA_LLC_NBITS,
+    TETRA_LLC_HEAD, TETRA_LLC_FCS, TETRA_LLC_FCS_RX, TETRA_LLC_FCS_CALC, TETRA_LLC_FIELDS = 10
+};
+enum { TETRA_LLC_OK = 0, TETRA_LLC_NONE, TETRA_LLC_MALFORMED, TETRA_LLC_ENCRYPTED, TETRA_LLC_UNSUPPORTED };
+enum { TETRA_FCS_NONE = 0, TETRA_FCS_GOOD, TETRA_FCS_BAD };
+int tetra_etsi_llc(tetra_ctx *ctx, size_t C, size_t G, const int32_t *nblock, const int32_t *blocks,
+                   const int32_t *npdu, const int32_t *pdus, const int32_t *sdu /*[C][MAXJ][MAXPDU][8]*/,
+                   const uint8_t *sdu_data /*[C][MAXJ][40]*/, int32_t maxd, const int32_t *ndone /*[C/G]*/,
+                   const int32_t *done /*[C/G][maxd][13]*/, const uint8_t *done_data /*[C/G][maxd][512]*/,
+                   int32_t *llc /*[C][MAXJ][MAXPDU][10]*/, uint8_t *tl /*[C][MAXJ][40]*/,
+                   int32_t *llc_done /*[C/G][maxd][10]*/, uint8_t *tl_done /*[C/G][maxd][512]*/);
+
 /* The ETSI receiver's AFC mixer on a streaming window: out [C][N] cf32 = iq (cf32 rows ld samples
  * apart) x exp(-j 2 pi f (n0 + n) / fs), n0 = the window's first sample in the capture (frequency_shift's
  * float64 arithmetic, processor.py:85-100, with one continuous phase across windows); mix_c [C] as

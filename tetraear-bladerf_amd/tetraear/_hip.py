@@ -106,6 +106,11 @@ ETSI_FRAG_CHAIN = __import__("numpy").dtype([("last_bit", "<i8"), ("active", "<i
                                             ("data", "u1", (SDU_MAXBYTES,))])
 ETSI_FRAG = __import__("numpy").dtype([("bit0", "<i8"), ("dropped", "<i4"), ("orphans", "<i4"),
                                       ("chain", ETSI_FRAG_CHAIN, (FRAG_CHAINS,))])
+# tetra_etsi_llc (include/tetra_hip.h): the LLC records
+(LLC_STATUS, LLC_TYPE, LLC_NR, LLC_NS, LLC_OFFSET, LLC_NBITS, LLC_HEAD, LLC_FCS, LLC_FCS_RX, LLC_FCS_CALC,
+ LLC_FIELDS) = range(11)
+LLC_OK, LLC_NONE, LLC_MALFORMED, LLC_ENCRYPTED, LLC_UNSUPPORTED = range(5)
+FCS_NONE, FCS_GOOD, FCS_BAD = range(3)
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -190,6 +195,8 @@ def _bind(L):
                                       _vp]),
         "tetra_etsi_sdu": (_i32, [_vp, _vp, _sz, _sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
+        "tetra_etsi_llc": (_i32, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp]),
         "tetra_etsi_mix": (_i32, [_vp, _vp, _sz, _sz, _sz, _vp, ctypes.c_double, ctypes.c_int64, _vp]),
         "tetra_etsi_decode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
         "tetra_etsi_encode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp]),

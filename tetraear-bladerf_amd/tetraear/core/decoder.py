@@ -90,7 +90,7 @@ class TetraDecoder:
 
     def __init__(self, key_manager=None, auto_decrypt: bool = True, mode=None, mac: bool = False,
                  link_quality: bool = False, vote: bool = False, timebase_vote: bool = False,
-                 traffic: bool = False, sdu: bool = False):
+                 traffic: bool = False, sdu: bool = False, llc: bool = False):
         self.SYNC_PATTERN = [0, 1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0,
                              1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0]
         self.FRAME_LENGTH = 510
@@ -111,6 +111,8 @@ class TetraDecoder:
         self.etsi_traffic = bool(traffic)
         # mode="etsi", mac=True: TM-SDUs and joined fragments from the device records (EtsiLowerMac(sdu=True))
         self.etsi_sdu = bool(sdu)
+        # mode="etsi", mac=True, sdu=True: every TM-SDU read as an LLC PDU (EtsiLowerMac(llc=True))
+        self.etsi_llc = bool(llc)
 
     # ------------------------------------------------------------------ keys and the reference's rest
     def set_keys(self, keys):
@@ -468,6 +470,8 @@ class TetraDecoder:
                                   length=p.get("length", 0), data=p["sdu"], fill_bits=p.get("fill", 0),
                                   encryption_mode=mode, reassembled_data=whole))
                 extra.append({"sdu_bits": p["sdu_bits"], "role": p["role"]})
+                if "llc" in p:
+                    extra[-1]["llc"] = p["llc"]
         return out, extra
 
     def _etsi_rx(self):
@@ -475,5 +479,5 @@ class TetraDecoder:
             from tetraear.core.etsi import EtsiLowerMac
             self._etsi = EtsiLowerMac(mac=self.etsi_mac, link_quality=self.etsi_link_quality, vote=self.etsi_vote,
                                       timebase_vote=self.etsi_timebase_vote, traffic=self.etsi_traffic,
-                                      sdu=self.etsi_sdu)
+                                      sdu=self.etsi_sdu, llc=self.etsi_llc)
         return self._etsi

@@ -18,6 +18,9 @@ a slot the control decoders could not read comes out as descrambled type-4 soft 
 With ``sdu=True`` (and ``mac=True``) tetra_etsi_sdu (k_sdu_walk, k_sdu_join) follows the MAC call: every PDU
 gets its TM-SDU, and a carrier's fragments are joined across bursts and calls; ``messages`` lists the
 finished TM-SDUs for an upper MAC.
+With ``llc=True`` (and ``sdu=True``) tetra_etsi_llc (k_llc_whole, k_llc_done) follows: every TM-SDU is read as an
+LLC PDU -- type, sequence bits, the frame check sequence, the TL-SDU byte-aligned -- and ``link_messages``
+lists the messages whose LLC PDU reads well.
 """
 import numpy as np
 
@@ -281,12 +284,72 @@ def done_dict(rec, data, block):
             "gaps": r[_hip.DONE_GAPS], "block": block, "pdu": r[_hip.DONE_PDU]}
 
 
+def run_llc(c, G, nk, blocks, npdu, pdus, sd):
+    """tetra_etsi_llc on host arrays behind run_sdu, sd = what run_sdu returned: (llc [C, MAXJ, MAXPDU, 10],
+    tl [C, MAXJ, 40], llc_done [C / G, maxd, 10], tl_done [C / G, maxd, 512])."""
+    sdu, sdu_data, ndone, done, done_data = sd
+    C, maxd = len(nk), done.shape[1]
+    llc = np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.LLC_FIELDS), np.int32)
+    tl = np.zeros((C, _hip.ETSI_MAXJ, _hip.SDU_ROW), np.uint8)
+    llc_done = np.zeros((C // G, maxd, _hip.LLC_FIELDS), np.int32)
+    tl_done = np.zeros((C // G, maxd, _hip.SDU_MAXBYTES), np.uint8)
+    c.check(c.lib.tetra_etsi_llc(c.handle, C, G, _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(npdu), _hip.ptr(pdus),
+                                 _hip.ptr(sdu), _hip.ptr(sdu_data), maxd, _hip.ptr(ndone), _hip.ptr(done),
+                                 _hip.ptr(done_data), _hip.ptr(llc), _hip.ptr(tl), _hip.ptr(llc_done), _hip.ptr(tl_done)),
+            "tetra_etsi_llc")
+    return llc, tl, llc_done, tl_done
+
+
+# Host-side names, transcribed from EN 300 392-2 (clause 21 the LLC PDU types, clause 18 the MLE protocol
+# discriminator, clause 14 the CMCE downlink PDU types) and NOT pinned against a conformance vector: the
+# device records carry the raw TYPE and HEAD, so a correction is a change to these tables.
+LLC_NAMES = ("BL-ADATA", "BL-DATA", "BL-UDATA", "BL-ACK", "BL-ADATA+FCS", "BL-DATA+FCS", "BL-UDATA+FCS", "BL-ACK+FCS",
+             "AL-SETUP", "AL-DATA/AL-FINAL", "AL-UDATA/AL-UFINAL", "AL-ACK/AL-RNR", "AL-RECONNECT", "SUPPLEMENTARY",
+             "L2-SIGNALLING", "AL-DISC")
+MLE_PROTOCOLS = {1: "MM", 2: "CMCE", 4: "SNDCP", 5: "MLE", 6: "MANAGEMENT"}   # the rest reserved
+PDU_TYPE_BITS = {1: 4, 2: 5, 4: 4, 5: 3}   # the PDU type field behind the discriminator
+CMCE_DOWNLINK = ("D-ALERT", "D-CALL-PROCEEDING", "D-CONNECT", "D-CONNECT-ACKNOWLEDGE", "D-DISCONNECT", "D-INFO",
+                 "D-RELEASE", "D-SETUP", "D-STATUS", "D-TX-CEASED", "D-TX-CONTINUE", "D-TX-GRANTED", "D-TX-WAIT",
+                 "D-TX-INTERRUPT", "D-CALL-RESTORE", "D-SDS-DATA", "D-FACILITY")
+
+
+def llc_keys(rec, row):
+    """One tetra_etsi_llc record and the bytes from its TL-SDU's first byte on (tl at the SDU's BYTE, or the
+    tl_done row) as the dict a pdu, or an entry of ``sdus``, gains under ``llc``: ``status`` (0 ok, 1 none,
+    2 malformed, 3 encrypted, 4 unsupported), ``type`` and ``name`` (None where not read), ``nr`` / ``ns``
+    (None where the type has none), ``fcs`` (None: the type has none; True good, False bad), ``fcs_rx``,
+    ``fcs_calc``, ``tl_sdu`` (bytes, MSB first, zero-padded), ``tl_sdu_bits``, ``protocol`` (the MLE protocol
+    discriminator, None with fewer than 3 bits) and ``protocol_name``, ``pdu_type`` (None when the TL-SDU's
+    first eight bits hold fewer bits than the protocol's type field, or the protocol has no table) and
+    ``pdu_name`` (the CMCE downlink names; else None)."""
+    r = [int(v) for v in rec]
+    status, t, head = r[_hip.LLC_STATUS], r[_hip.LLC_TYPE], r[_hip.LLC_HEAD]
+    read = status in (_hip.LLC_OK, _hip.LLC_UNSUPPORTED)
+    n = r[_hip.LLC_NBITS] if status == _hip.LLC_OK else 0
+    d = {"status": status, "type": t if read else None, "name": LLC_NAMES[t] if read else None,
+         "nr": None if r[_hip.LLC_NR] < 0 else r[_hip.LLC_NR], "ns": None if r[_hip.LLC_NS] < 0 else r[_hip.LLC_NS],
+         "fcs": {_hip.FCS_GOOD: True, _hip.FCS_BAD: False}.get(r[_hip.LLC_FCS]),
+         "fcs_rx": r[_hip.LLC_FCS_RX] & 0xFFFFFFFF, "fcs_calc": r[_hip.LLC_FCS_CALC] & 0xFFFFFFFF,
+         "tl_sdu": bytes(row[:(n + 7) // 8]), "tl_sdu_bits": n, "protocol": None, "protocol_name": None,
+         "pdu_type": None, "pdu_name": None}
+    if status == _hip.LLC_OK and head >= 0:
+        pd = head >> 5
+        d["protocol"], d["protocol_name"] = pd, MLE_PROTOCOLS.get(pd, "RESERVED")
+        w = PDU_TYPE_BITS.get(pd)
+        if w is not None and n >= 3 + w:
+            d["pdu_type"] = (head >> (5 - w)) & ((1 << w) - 1)
+            if pd == 2 and d["pdu_type"] < len(CMCE_DOWNLINK):
+                d["pdu_name"] = CMCE_DOWNLINK[d["pdu_type"]]
+    return d
+
+
 def messages(frames):
     """One carrier's frames (sdu=True) -> its finished TM-SDUs in time order, what a caller hands to an
     upper MAC: of every frame the whole ones -- a MAC-RESOURCE that is no fragment, with a TM-SDU of at
     least one bit, sdu_status 0 or 3 (encrypted: ``enc`` != 0, the bits untouched) -- in block and PDU order,
     then the ones a MAC-END of the frame completed (``sdus``).  Each is a dict(ssi, address_type, aux, enc,
-    nbits, data, fragments, span_slots, gaps, position[, tn, fn, mn]); a whole one has fragments 1, gaps 0."""
+    nbits, data, fragments, span_slots, gaps, position[, tn, fn, mn]); a whole one has fragments 1, gaps 0.
+    With llc=True each carries its ``llc`` dict (llc_keys) as well."""
     out = []
     for f in frames:
         where = {k: f[k] for k in ("position", "tn", "fn", "mn") if k in f}
@@ -297,8 +360,24 @@ def messages(frames):
                     out.append(dict(ssi=p["ssi"], address_type=p["address_type"], aux=p["aux"],
                                     enc=p["encryption_mode"], nbits=p["sdu_bits"], data=p["sdu"], fragments=1,
                                     span_slots=0, gaps=0, **where))
+                    if "llc" in p:
+                        out[-1]["llc"] = p["llc"]
         for m in f.get("sdus", ()):
             out.append(dict(m, **where))
+    return out
+
+
+def link_messages(frames, drop_bad_fcs=True):
+    """One carrier's frames (llc=True) -> the messages of ``messages(frames)`` whose LLC PDU reads ok (status
+    0), each with ``tl_sdu``, ``tl_sdu_bits``, ``protocol_name``, ``pdu_name`` and ``fcs`` beside its ``llc``
+    dict: what an MLE router consumes.  A message whose FCS is bad (``fcs`` False) is left out unless
+    drop_bad_fcs is False; one without an FCS (``fcs`` None) is kept: nothing vouches for it."""
+    out = []
+    for m in messages(frames):
+        ll = m.get("llc")
+        if ll is None or ll["status"] != _hip.LLC_OK or (drop_bad_fcs and ll["fcs"] is False):
+            continue
+        out.append(dict(m, **{k: ll[k] for k in ("tl_sdu", "tl_sdu_bits", "protocol_name", "pdu_name", "fcs")}))
     return out
 
 
@@ -358,15 +437,22 @@ class EtsiLowerMac:
     address_type, aux, enc, nbits, data, fragments, span_slots, gaps).  The fragment state is carried like
     the timebase: per channel by decode_stream / decode, cleared by reset_stream(), fresh for every
     decode_batch; ``frag_stats`` counts the chains dropped unfinished and the fragments that found no
-    chain.  ``messages(frames)`` lists a carrier's finished TM-SDUs.  Everything else is unchanged."""
+    chain.  ``messages(frames)`` lists a carrier's finished TM-SDUs.  Everything else is unchanged.
+
+    ``llc=True`` (with ``mac=True, sdu=True``): tetra_etsi_llc runs after the SDU call.  Every pdu dict and
+    every entry of ``sdus`` gains ``llc`` (llc_keys): the LLC type, sequence bits, the FCS verdict and the
+    TL-SDU; ``link_messages(frames)`` lists the messages that read well.  Everything else is unchanged."""
 
     def __init__(self, mcc=None, mnc=None, colour_code=None, mac=False, link_quality=False, vote=False,
                  vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, timebase_vote=False,
-                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False):
+                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False, llc=False):
         self.mac = bool(mac)
         self.sdu = bool(sdu)
         if self.sdu and not self.mac:
             raise ValueError("sdu=True reads the PDU records of mac=True")
+        self.llc = bool(llc)
+        if self.llc and not self.sdu:
+            raise ValueError("llc=True reads the TM-SDUs of mac=True, sdu=True")
         self.traffic = bool(traffic)
         self.link_quality = bool(link_quality)
         self.timebase_vote, self.tdma_cap = bool(timebase_vote), int(tdma_cap)
@@ -422,6 +508,8 @@ class EtsiLowerMac:
         self._frag_last = frag
         sd = run_sdu(c, nsym, 1, 0, 0, nb, bursts, nk, blocks, t1, mac[1], mac[2], None, frag)
         self._lost += np.maximum(sd[2] - SDU_MAXD, 0)
+        if self.llc:   # the LLC records ride behind the SDU call's five arrays
+            sd += run_llc(c, 1, nk, blocks, mac[1], mac[2], sd)
         return sd
 
     @property
@@ -640,7 +728,8 @@ class EtsiLowerMac:
     def _frames(C, nb, bursts, nk, blocks, t1, mac=None, lq=None, tr=None, sd=None, G=1):
         """mac: None, or tetra_etsi_mac's (slots, npdu, pdus) for the same call; lq: None, or
         tetra_etsi_link_quality's (bq, kq); tr: None, or tetra_etsi_traffic's (tq, tch, has_cell [C]); sd:
-        None, or tetra_etsi_sdu's (sdu, sdu_data, ndone, done, done_data) over groups of G rows."""
+        None, or tetra_etsi_sdu's (sdu, sdu_data, ndone, done, done_data) over groups of G rows, with
+        tetra_etsi_llc's (llc, tl, llc_done, tl_done) behind them when llc=True."""
         out = []
         for ch in range(C):
             frames = []
@@ -659,6 +748,8 @@ class EtsiLowerMac:
                         if sd is not None:
                             for q, p in enumerate(blks[-1]["pdus"]):
                                 p.update(sdu_keys(sd[0][ch, j, q], sd[1][ch, j]))
+                                if len(sd) > 5:
+                                    p["llc"] = llc_keys(sd[5][ch, j, q], sd[6][ch, j, int(sd[0][ch, j, q, _hip.SDU_BYTE]):])
                     if lq is not None:
                         blks[-1].update(block_quality(lq[1][ch, j], k))
                 frames.append({"position": start, "burst": BURST_NAMES[kind], "burst_kind": kind,
@@ -680,6 +771,8 @@ class EtsiLowerMac:
                     row, b = int(sd[3][g, i, _hip.DONE_ROW]), int(sd[3][g, i, _hip.DONE_BURST])
                     blk = int(blocks[row, int(sd[3][g, i, _hip.DONE_BLOCK]), 3])
                     out[row][b].setdefault("sdus", []).append(done_dict(sd[3][g, i], sd[4][g, i], blk))
+                    if len(sd) > 5:
+                        out[row][b]["sdus"][-1]["llc"] = llc_keys(sd[7][g, i], sd[8][g, i])
         return out
 
     def decode(self, symbols, soft_bits=None, stream=True):

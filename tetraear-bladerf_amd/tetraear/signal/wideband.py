@@ -233,7 +233,7 @@ class WidebandReceiver:
 
 
     def decode(self, x, cells, mac=False, timebase=False, tol=64, link_quality=False,
-               tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False):
+               tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False, llc=False):
         """x [Nw] -> per carrier the frames decoded from it, each burst once (merge_chunks), in row
         order: demod, then the ETSI lower MAC on every (carrier, chunk) with carrier k's scrambling
         init cells[k].  A frame is the lower MAC's dict (core/etsi.py) plus "chunk" and "sample" (its
@@ -264,13 +264,16 @@ class WidebandReceiver:
         elements, and the frame whose MAC-END completed a chain of fragments gains ``sdus``, as
         EtsiLowerMac(sdu=True)'s frames carry them (core/etsi.py messages() lists a carrier's finished
         TM-SDUs); ``frag_stats`` holds the call's dropped / orphans per carrier and ``lost``, the messages
-        completed beyond the SDU_MAXD (core/etsi.py) a call returns per carrier, which reach no frame."""
+        completed beyond the SDU_MAXD (core/etsi.py) a call returns per carrier, which reach no frame.
+        llc=True (needs sdu=True, else ValueError): one tetra_etsi_llc call over the same groups; every pdu
+        dict and every entry of ``sdus`` gains ``llc`` (core/etsi.py llc_keys; link_messages() lists the
+        messages whose LLC PDU reads well)."""
         return self._decode(x, np.asarray(cells, np.uint32), None, mac, timebase, tol, link_quality=link_quality,
-                            tdma_cap=tdma_cap, traffic=traffic, sdu=sdu)[0]
+                            tdma_cap=tdma_cap, traffic=traffic, sdu=sdu, llc=llc)[0]
 
     def decode_acquire(self, x, cell_init, mac=False, timebase=False, tol=64, link_quality=False, score=None,
                        vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT,
-                       traffic=False, acquired=None, sdu=False):
+                       traffic=False, acquired=None, sdu=False, llc=False):
         """decode without given cells: cell_init [M] holds each carrier's scrambling init before the
         capture (3 = unknown); every carrier's cell comes from the last CRC-good BSCH over all of its
         chunk rows, and all of its rows are descrambled with it (tetra_lmac_etsi_acquire_groups, G =
@@ -286,7 +289,7 @@ class WidebandReceiver:
         default cell_init[k] == 3 -- reports ``usage`` None (its blocks were descrambled with no cell, so
         a failed CRC says nothing).  The default misreads a carrier whose known cell is all zero (MCC =
         MNC = colour code = 0), which has the init of "unknown": pass ``acquired`` for such a carrier, as
-        WidebandStream does from piece to piece.  sdu=True: decode's."""
+        WidebandStream does from piece to piece.  sdu=True, llc=True: decode's."""
         state = np.array(cell_init, np.uint32)
         if state.shape != (self.plan.M,):
             raise ValueError(f"cell_init holds {state.shape} inits, the receiver has {self.plan.M} carriers")
@@ -295,13 +298,14 @@ class WidebandReceiver:
             raise ValueError(f"score must be a C-contiguous int32 array of {self.plan.M} (it is updated in place)")
         had = state != 3 if acquired is None else np.asarray(acquired, bool)
         frames, ngood = self._decode(x, None, state, mac, timebase, tol, link_quality=link_quality, score=score,
-                                     vote_cap=vote_cap, tdma_cap=tdma_cap, traffic=traffic, acquired=had, sdu=sdu)
+                                     vote_cap=vote_cap, tdma_cap=tdma_cap, traffic=traffic, acquired=had, sdu=sdu,
+                                     llc=llc)
         return frames, state, ngood
 
     def _decode(self, x, cells, state, mac, timebase=False, tol=64, tdma=None, advance=0, link_quality=False,
                 score=None, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_score=None,
                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, acquired=None, sdu=False, frag=None,
-                walked=None):
+                walked=None, llc=False):
         """The chain behind decode (cells [M]) and decode_acquire (state [M], updated in place; score [M]
         int32 or None, likewise: the vote): (frames, ngood or None).  timebase: tdma [M] ETSI_TDMA (in/out; None: new streams), whose bit0
         moves on by ``advance`` bits after the call (WidebandStream).  timebase="vote": tdma_score [M] int32
@@ -309,12 +313,15 @@ class WidebandReceiver:
         the MAC call; acquired [M] bool: the carriers that had a cell before the call (acquisition).
         sdu: tetra_etsi_sdu after the MAC call with its keep; frag [M] ETSI_FRAG (in/out; None: new
         streams), whose bit0 moves on by ``advance`` too; walked [M] (72 kHz samples of this buffer, or
-        None): a carrier's bursts up to there were walked from the previous buffer and feed nothing now."""
-        from tetraear.core.etsi import EtsiLowerMac, run_link_quality, run_sdu, run_traffic
+        None): a carrier's bursts up to there were walked from the previous buffer and feed nothing now.
+        llc: tetra_etsi_llc after the SDU call, over the same groups."""
+        from tetraear.core.etsi import EtsiLowerMac, run_link_quality, run_llc, run_sdu, run_traffic
         if timebase not in (False, True, "vote"):
             raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
         if sdu and not (mac and timebase):
             raise ValueError("sdu=True reads the PDU records of mac=True and the keep of timebase=True or 'vote'")
+        if llc and not sdu:
+            raise ValueError("llc=True reads the TM-SDUs of sdu=True")
         if timebase and (self.m2 % 2 or tol % 2 or tol < 0):
             raise ValueError(f"timebase=True works in bits: m2 ({self.m2}) and tol ({tol}) must be even")
         if timebase == "vote" and int(tdma_cap) <= 0:
@@ -383,6 +390,8 @@ class WidebandReceiver:
                 sd = run_sdu(c, None, nchunk, self.m2 // 2, advance, nb, bursts, nk, blocks, t1, npdu, recs, fed, frag)
                 self.frag_stats = {"dropped": frag["dropped"].copy(), "orphans": frag["orphans"].copy(),
                                    "lost": np.maximum(sd[2].astype(np.int64) - sd[3].shape[1], 0)}
+                if llc:
+                    sd += run_llc(c, nchunk, nk, blocks, npdu, recs, sd)
             keep = keep.astype(bool)
             pdus = (slots, npdu, recs)
         else:
@@ -448,6 +457,7 @@ class WidebandStream:
     is carried from piece to piece in ``frag`` [M] with the advance of ``tdma`` (reset() clears it), and
     the carried tail's bursts, decoded again, feed nothing a second time.  ``frag_stats``: the chains
     dropped and the orphans per carrier since reset().
+    ``llc=True`` (with ``sdu=True``): the pdu dicts and the ``sdus`` entries carry ``llc`` (WidebandReceiver.decode).
     ``vote=True`` (acquisition only): a carrier's cell is chosen by the vote over each buffer's BSCH
     blocks (WidebandReceiver.decode_acquire(score=...)), the score it gathers carried from piece to piece
     in ``cell_score`` and read as ``cell_scores`` (reset() clears it).  A burst in the carried tail is
@@ -461,13 +471,16 @@ class WidebandStream:
 
     def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False, timebase=False,
                  link_quality=False, vote=False, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT,
-                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False):
+                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False, llc=False):
         if timebase not in (False, True, "vote"):
             raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
         self.traffic = bool(traffic)
         self.sdu = bool(sdu)
         if self.sdu and not (mac and timebase):
             raise ValueError("sdu=True reads the PDU records of mac=True and the keep of timebase=True or 'vote'")
+        self.llc = bool(llc)
+        if self.llc and not self.sdu:
+            raise ValueError("llc=True reads the TM-SDUs of sdu=True")
         self.rx = WidebandReceiver(fs, M, m2, oversample)
         self.acquire, self.mac, self.timebase = cells is None, bool(mac), bool(timebase)
         self.tdma_vote, self.tdma_cap = timebase == "vote", int(tdma_cap)
@@ -534,7 +547,8 @@ class WidebandStream:
                                             score=self.cell_score, vote_cap=self.vote_cap,
                                             tdma_score=self.tdma_score, tdma_cap=self.tdma_cap, traffic=self.traffic,
                                             acquired=self.acquired, sdu=self.sdu, frag=self.frag,
-                                            walked=self.last - self.y0 + self.tol if self.sdu else None)
+                                            walked=self.last - self.y0 + self.tol if self.sdu else None,
+                                            llc=self.llc)
             if self.acquire:
                 self.cell_state = state
                 self.acquired |= ngood > 0
