@@ -228,10 +228,10 @@ def test_traffic_streams_and_slot_usage():
 
 
 def test_frames_gain_the_keys_only_with_traffic():
-    """EtsiLowerMac._frames on hand-made records: without the traffic records the frames have today's key
+    """build_frames on hand-made records: without the traffic records the frames have today's key
     set; with them every frame gains usage and traffic, None for a channel without a cell."""
     from tetraear import _hip
-    from tetraear.core.etsi import EtsiLowerMac, traffic_keys
+    from tetraear.core.etsi import EtsiLowerMac, LowerMac, Traffic, build_frames, traffic_keys
     nb, nk = np.array([3, 1], np.int32), np.array([3, 1], np.int32)
     bursts = np.zeros((2, 8, 2), np.int32)
     bursts[0, :3] = [(10, 0), (520, 2), (1030, 1)]
@@ -239,13 +239,14 @@ def test_frames_gain_the_keys_only_with_traffic():
     blocks = np.zeros((2, 16, 4), np.int32)
     blocks[0, :3] = [(0, 0, 0, 0), (2, 1, 1, 0), (1, 1, 2, 0)]
     t1 = np.zeros((2, 16, 268), np.uint8)
-    plain = EtsiLowerMac._frames(2, nb, bursts, nk, blocks, t1)
+    lm = LowerMac(nb, bursts, nk, blocks, t1)
+    plain = build_frames(lm)
     assert all(set(f) == {"position", "burst", "burst_kind", "timeslot", "blocks", "crc_ok"} for fr in plain for f in fr)
     tq = np.full((2, 8, 4), -1, np.int32)
     tq[0, :3] = [(_hip.TCH_FULL, 432, 999, 2), (_hip.TCH_NONE, 0, 0, 0), (_hip.TCH_HALF, 216, 500, 1)]
     tq[1, 0] = (_hip.TCH_FULL, 432, 7, 0)
     tch = np.arange(2 * 8 * 432).reshape(2, 8, 432).astype(np.int8)
-    got = EtsiLowerMac._frames(2, nb, bursts, nk, blocks, t1, None, None, (tq, tch, np.array([True, False])))
+    got = build_frames(lm, tr=Traffic(tq, tch, np.array([True, False])))
     assert [{k: v for k, v in f.items() if k not in ("usage", "traffic", "blocks")} for fr in got for f in fr] == \
         [{k: v for k, v in f.items() if k != "blocks"} for fr in plain for f in fr]
     assert [f["usage"] for f in got[0]] == ["traffic", "sync", "stolen"] and got[1][0]["usage"] is None

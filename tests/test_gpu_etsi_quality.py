@@ -3,6 +3,7 @@ the model's, integer for integer, on rows built on the CPU, on streaming and gro
 smallest real chain and on a seeded sweep; then the Python surface.  No tolerance anywhere.
 tests/test_etsi_quality_model.py proves on the CPU that the built rows mean what is assumed here."""
 import functools
+import itertools
 import os
 
 import numpy as np
@@ -201,7 +202,10 @@ def test_stream_rows_alternate_and_read_the_whole_stream():
 
 # ------------------------------------------------------------------------------ 5. groups
 
-def test_groups_are_scored_with_the_acquired_cell():
+@functools.lru_cache(maxsize=None)
+def _two_groups():
+    """C = 6 rows in G = 3 groups through tetra_lmac_etsi_acquire_groups: (hard, soft, the lower MAC's outputs,
+    the cells after the call, the cells A and B the rows were built with)."""
     rng = np.random.default_rng(55)
     rows, _, A = LG.case_sync_in_row(rng, 2)   # the only SB in the group's last row
     B, _ = R.cell_fields(rng)
@@ -209,6 +213,11 @@ def test_groups_are_scored_with_the_acquired_cell():
     hard, soft, nsym = LG.pack(rows)
     out, want, after, good = LG.check_groups(hard, soft, nsym, 3, [3, 3], "quality groups")
     assert after == [A, 3] and good == [1, 0]
+    return hard, soft, out, after, A, B
+
+
+def test_groups_are_scored_with_the_acquired_cell():
+    hard, soft, out, after, A, B = _two_groups()
     bq, kq = check(soft, hard, 0, 3, np.array(after, np.uint32), poison_unwritten(out), "groups")
     for ch in range(6):
         for j in range(int(out["nblock"][ch])):
@@ -219,6 +228,27 @@ def test_groups_are_scored_with_the_acquired_cell():
     # the cell is the call's argument, not the context's table: another cell reads errors on the same rows
     _, _, kq2 = Q.call(soft, hard, 0, 3, np.array([B, 3], np.uint32), out)
     assert kq2[0, 0, Q.NERR] > 50
+
+
+@pytest.mark.parametrize("on_device", list(itertools.product((False, True), repeat=3)),
+                         ids=lambda c: "".join("dh"[not d] for d in c))
+def test_small_arrays_host_and_device_mixed(on_device):
+    """cell_init, nburst and nblock share one staged input: with any of them a device pointer and the rest the
+    host's, both outputs are the all-host call's byte for byte (all three on the device: no staged pack)."""
+    import torch
+    from tetraear import _hip
+    hard, soft, out, after, _, _ = _two_groups()
+    o = poison_unwritten(out)
+    rc, bq, kq = Q.call(soft, hard, 0, 3, np.array(after, np.uint32), o)
+    assert rc == 0 and (kq[:3, 0, Q.NERR] == 0).all()
+    small = [np.array(after, np.uint32).view(np.int32), o["nburst"], o["nblock"]]
+    held = [torch.from_numpy(np.ascontiguousarray(a)).cuda() if d else a for a, d in zip(small, on_device)]
+    torch.cuda.synchronize()
+    gb, gk = np.full_like(bq, Q.POISON), np.full_like(kq, Q.POISON)
+    c = _hip.ctx()
+    p = [_hip.ptr(a) for a in (soft, hard, held[0], held[1], o["bursts"], held[2], o["blocks"], o["type1"], gb, gk)]
+    c.check(c.lib.tetra_etsi_link_quality(c.handle, p[0], p[1], 6, hard.shape[1], 0, 3, *p[2:]), str(on_device))
+    assert gb.tobytes() == bq.tobytes() and gk.tobytes() == kq.tobytes()
 
 
 # ------------------------------------------------------------------------------ 6. the smallest real chain

@@ -41,9 +41,13 @@ def poisoned_outputs(seed, C, G, maxd):
             rng.integers(0, 256, (C // G, nd, S.SDU_MAXBYTES)).astype(np.uint8)]
 
 
-def call_sdu(call, frag, outs, device=False):
+SMALL = {"nsym": 0, "nburst": 1, "nblock": 3, "npdu": 6, "keep": 8}   # the arrays that share one staged input
+
+
+def call_sdu(call, frag, outs, device=False, mixed=()):
     """tetra_etsi_sdu on host arrays or (device) on torch tensors, the type-1 tensor at an odd address;
-    frag and outs are updated in place.  Returns the return code."""
+    frag and outs are updated in place.  mixed: the names of SMALL passed as device tensors in a call
+    whose other arrays are the host's.  Returns the return code."""
     from tetraear import _hip
     c = _hip.ctx()
     arrays = [None if a is None else np.ascontiguousarray(a) for a in call["arrays"]]
@@ -60,6 +64,12 @@ def call_sdu(call, frag, outs, device=False):
         p = [_hip.ptr(a) for a in dev]
     else:
         p = [_hip.ptr(a) for a in args]
+    if mixed:
+        import torch
+        held = {SMALL[k]: torch.from_numpy(np.ascontiguousarray(args[SMALL[k]])).cuda() for k in mixed}
+        torch.cuda.synchronize()
+        for i, t in held.items():
+            p[i] = _hip.ptr(t)
     rc = c.lib.tetra_etsi_sdu(c.handle, p[0], C, call["G"], call["row_bits"], call["advance"], call["gap_slots"],
                               p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11], call["maxd"],
                               p[12], p[13], p[14])
@@ -179,6 +189,61 @@ def test_one_row_groups_equal_the_streaming_form():
         other = dict(call, keep=np.ones((1, S.MAXB), np.int32), advance=2 * (int(call["nsym"][0]) - 1))
         b, _ = check_call(other, fb, mb, 1000 + k, what="keep")
         assert all(np.array_equal(x, y) for x, y in zip(a, b)) and fa.tobytes() == fb.tobytes()
+
+
+@functools.lru_cache(maxsize=None)
+def two_groups_call():
+    """C = 6, G = 3, maxd = 4: two groups of three overlapping rows, a chain of three and of two fragments
+    that both complete in the call (the model says so)."""
+    rng = np.random.default_rng(77)
+    per = []
+    for nfrag, ssi in ((3, 0x111111), (2, 0x222222)):
+        sdu = K.payload(rng, K.sdu_len(rng, nfrag))
+        per.append(K.Scenario(f"G 3, {nfrag} fragments", K.chain_bursts(rng, sdu, nfrag, 300, ssi=ssi), G=3).calls(rng)[0])
+    call = dict(per[0], nsym=np.concatenate([c["nsym"] for c in per]), keep=np.concatenate([c["keep"] for c in per]),
+                arrays=tuple(np.concatenate([c["arrays"][i] for c in per]) for i in range(7)))
+    assert (call["G"], call["maxd"], len(call["arrays"][0])) == (3, 4, 6)
+    _, ndone, _ = S.run([S.Frag(), S.Frag()], 3, call["row_bits"], call["advance"], call["gap_slots"], 4, call["nsym"],
+                        *call["arrays"], keep=call["keep"])
+    assert ndone.tolist() == [1, 1]
+    return call
+
+
+def _run_two_groups(call, mixed=(), models=None):
+    """Every output of one call from fresh fragment state, as bytes (models: one Frag a group; default two)."""
+    frag = frag_array(models or [S.Frag(), S.Frag()])
+    outs = poisoned_outputs(4400, len(call["arrays"][0]), call["G"], call["maxd"])
+    assert call_sdu(call, frag, outs, mixed=mixed) == 0, mixed
+    return [o.tobytes() for o in outs] + [frag.tobytes()]
+
+
+@pytest.mark.parametrize("mixed", sorted(SMALL), ids=sorted(SMALL))
+def test_one_small_array_on_the_device(mixed):
+    """The small arrays share one staged input: with any one of them a device pointer the others still land at
+    their own offsets, and every output is the all-host call's, byte for byte."""
+    call = two_groups_call()
+    assert _run_two_groups(call, (mixed,)) == _run_two_groups(call)
+
+
+def test_small_arrays_without_keep_and_one_on_the_device():
+    call = dict(two_groups_call(), keep=None)
+    want = _run_two_groups(call)
+    assert want != _run_two_groups(two_groups_call())   # (every copy feeds without keep: the call differs)
+    assert _run_two_groups(call, ("nblock",)) == want and _run_two_groups(call, ("nsym", "npdu")) == want
+
+
+def test_nsym_in_the_pack_of_the_streaming_form():
+    """Only the streaming form (G = 1, row_bits 0, no keep) reads nsym, the pack's first part: the 17 stacked rows
+    with nsym alone on the device, and with nsym alone on the host, against the all-host call."""
+    scs, calls = stacked_scenarios()
+    call = calls[0]
+    assert (call["G"], call["row_bits"], call["keep"], call["maxd"]) == (1, 0, None, 4)
+    models = [S.Frag(sc.bit0) for sc in scs]
+    want = _run_two_groups(call, models=models)
+    assert _run_two_groups(call, ("nsym",), models) == want
+    assert _run_two_groups(call, ("nburst", "nblock", "npdu"), models) == want
+    other = dict(call, nsym=call["nsym"] + 64)   # nsym is read: another chunk length moves the streams on otherwise
+    assert _run_two_groups(other, ("nsym",), models) == _run_two_groups(other, models=models) != want
 
 
 # ------------------------------------------------------------------------------ a seeded sweep

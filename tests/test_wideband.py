@@ -142,6 +142,42 @@ def test_wideband_stream_host_logic(monkeypatch):
         assert len(got[k]) == len(want) and all(0 <= g - w <= 3 for g, w in zip(got[k], want)), k
 
 
+def test_stream_hands_its_attributes_as_they_are_to_the_chain(monkeypatch):
+    """tdma, tdma_score, frag, cell_state, acquired and cell_score are plain attributes of the stream: one
+    assigned from outside (a stream resumed from saved state) is what the next buffer's chain is given, and
+    what the chain leaves is what the stream reads afterwards."""
+    from tetraear import _hip
+    from tetraear.signal import wideband as WB
+    seen = []
+
+    def fake_decode(self, x, cells, opt, tol, st):
+        seen.append(st)
+        st.tdma["bit0"] += 7
+        st.cell_state[:] = 99
+        self.frag_stats = {"lost": np.ones(len(st.frag), np.int64)}
+        return [[] for _ in range(len(st.tdma))], np.ones(len(st.tdma), np.int32)
+
+    monkeypatch.setattr(WB.WidebandReceiver, "_decode", fake_decode)
+    ws = WB.WidebandStream(mac=True, timebase="vote", sdu=True, llc=True, vote=True)
+    M = ws.M
+    saved = dict(tdma=np.zeros(M, _hip.ETSI_TDMA), tdma_score=np.full(M, 5, np.int32), frag=np.zeros(M, _hip.ETSI_FRAG),
+                 cell_state=np.full(M, 1234, np.uint32), acquired=np.zeros(M, bool), cell_score=np.full(M, 9, np.int32))
+    saved["tdma"]["bit0"] = 1000
+    for k, v in saved.items():
+        setattr(ws, k, v)
+    ws._decode_buffer(np.zeros(4, np.complex64), advance=6)
+    st = seen[0]
+    assert all(getattr(st, k) is saved[k] for k in ("tdma", "tdma_score", "frag", "acquired", "cell_score"))
+    assert st.advance == 6 and st.walked is not None and (saved["cell_state"] == 1234).all()   # cell_state: a copy in
+    assert ws.tdma is saved["tdma"] and (ws.tdma["bit0"] == 1007).all() and ws.frag is saved["frag"]
+    assert (ws.cell_state == 99).all() and ws.acquired.all() and ws.lost_sdus.tolist() == [1] * M
+    ws.reset()
+    assert ws.tdma is not saved["tdma"] and (ws.tdma["bit0"] == 0).all() and (ws.cell_state == 3).all()
+    ws.tdma_score = saved["tdma_score"]
+    ws._decode_buffer(np.zeros(4, np.complex64))
+    assert seen[1].tdma_score is saved["tdma_score"] and seen[1].tdma is ws.tdma and ws.tdma_scores.tolist() == [5] * M
+
+
 @pytest.fixture(scope="module")
 def capture():
     from tetraear.signal.wideband import synth_wideband

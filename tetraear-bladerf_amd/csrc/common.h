@@ -113,6 +113,14 @@ struct Staging {
     }
     void *pin_take(size_t bytes);   // 256-B aligned arena space, nullptr if none
     const void *in(const void *p, size_t bytes);
+    // Small arrays of 4-byte elements that share one staged input: those of `parts` in host memory are
+    // uploaded back to back and each p rewritten to its device address; device and null pointers stay.
+    // One pack per Staging (its host image may live in `packed` until finish()).  False: staging failed
+    // (finish() reports it).
+    struct Part { const void *p; size_t n; };
+    std::vector<int32_t> packed;   // the pack's host image where the arena has no room (lives until finish)
+    bool pack(Part *parts, size_t count);
+    template <size_t N> bool pack(Part (&parts)[N]) { return pack(parts, N); }
     void *out(void *p, size_t bytes);
     void *inout(void *p, size_t bytes);   // `in` + `out` on one buffer (host contents uploaded first)
     int finish();   // D2H copies (if any) + stream sync when host memory was involved

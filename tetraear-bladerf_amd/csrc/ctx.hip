@@ -65,25 +65,67 @@ void *Staging::pin_take(size_t bytes) {
     return (char *)ctx->pin + at;
 }
 
+// The next input slot with `bytes` of room and, if the arena has room, the pinned image to fill and
+// upload from (*pin; else nullptr: upload from the caller's memory).  nullptr: failed, error set.
+static void *in_slot(Staging &st, size_t bytes, void **pin) {
+    st.host_touched = true;
+    if (st.next_in > S_IN5) {
+        st.failed = true;
+        tetra_fail(st.ctx, TETRA_E_INVALID, "more than %d staged host inputs", S_IN5 - S_IN0 + 1);
+        return nullptr;
+    }
+    void *d = ws(st.ctx, st.next_in++, bytes);
+    if (!d) st.failed = true;
+    *pin = d ? st.pin_take(bytes) : nullptr;
+    return d;
+}
+
+static const void *upload(Staging &st, void *d, const void *h, size_t bytes) {
+    if (hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st.ctx->stream) == hipSuccess) return d;
+    st.failed = true;
+    tetra_fail(st.ctx, TETRA_E_HIP, "H2D staging copy failed");
+    return nullptr;
+}
+
 const void *Staging::in(const void *p, size_t bytes) {
     if (failed) return nullptr;
     if (bytes == 0) return p ? p : ws(ctx, next_in++, 16);
     if (is_device_ptr(p)) return p;
-    host_touched = true;
-    if (next_in > S_IN5) {
-        failed = true;
-        tetra_fail(ctx, TETRA_E_INVALID, "more than %d staged host inputs", S_IN5 - S_IN0 + 1);
-        return nullptr;
-    }
-    void *d = ws(ctx, next_in++, bytes);
-    void *h = d ? pin_take(bytes) : nullptr;
+    void *h, *d = in_slot(*this, bytes, &h);
+    if (!d) return nullptr;
     if (h) memcpy(h, p, bytes);
-    if (!d || hipMemcpyAsync(d, h ? h : p, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+    return upload(*this, d, h ? h : p, bytes);
+}
+
+bool Staging::pack(Part *parts, size_t count) {
+    if (failed) return false;
+    size_t total = 0;
+    uint32_t host = 0;   // bit i: parts[i] is host memory
+    for (size_t i = 0; i < count && i < 32; ++i)
+        if (parts[i].p && !is_device_ptr(parts[i].p)) {
+            host |= 1u << i;
+            total += parts[i].n;
+        }
+    if (count > 32 || (total && !packed.empty())) {   // `packed` holds one pack's image until finish()
         failed = true;
-        if (d) tetra_fail(ctx, TETRA_E_HIP, "H2D staging copy failed");
-        return nullptr;
+        tetra_fail(ctx, TETRA_E_INVALID, "Staging::pack: one pack of at most 32 arrays per call");
+        return false;
     }
-    return d;
+    if (total == 0) return true;
+    void *h, *d = in_slot(*this, total * 4, &h);
+    if (!d) return false;
+    if (!h) {
+        packed.resize(total);
+        h = packed.data();
+    }
+    size_t at = 0;
+    for (size_t i = 0; i < count; ++i)
+        if (host >> i & 1) {
+            memcpy((int32_t *)h + at, parts[i].p, parts[i].n * 4);
+            parts[i].p = (const int32_t *)d + at;
+            at += parts[i].n;
+        }
+    return upload(*this, d, h, total * 4) != nullptr;
 }
 
 void *Staging::out(void *p, size_t bytes) {

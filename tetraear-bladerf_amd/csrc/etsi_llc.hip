@@ -298,21 +298,11 @@ extern "C" int tetra_etsi_llc(tetra_ctx *ctx, size_t C, size_t G, const int32_t 
     const size_t NG = C / G;
     Staging st(ctx);
     // the int32 host inputs but the PDU and SDU records travel as one staged input (five staged inputs in all)
-    const int32_t *nk = nblock, *np = npdu, *nd = ndone, *bk = blocks, *dn = maxd > 0 ? done : nullptr;
-    struct Small { const int32_t **p; size_t n; } parts[] = {
-        {&nk, C}, {&np, C * MAXJ}, {&nd, NG}, {&bk, C * MAXJ * 4}, {&dn, NG * (size_t)maxd * ND}};
-    std::vector<int32_t> small;
-    for (auto &s : parts)
-        if (*s.p && !is_device_ptr(*s.p)) small.insert(small.end(), *s.p, *s.p + s.n);
-    if (!small.empty()) {
-        const int32_t *d = (const int32_t *)st.in(small.data(), small.size() * 4);
-        if (!d) return st.finish();
-        for (auto &s : parts)
-            if (*s.p && !is_device_ptr(*s.p)) {
-                *s.p = d;
-                d += s.n;
-            }
-    }
+    Staging::Part small[] = {{nblock, C}, {npdu, C * MAXJ}, {ndone, NG}, {blocks, C * MAXJ * 4},
+                             {maxd > 0 ? done : nullptr, NG * (size_t)maxd * ND}};
+    if (!st.pack(small)) return st.finish();
+    const int32_t *nk = (const int32_t *)small[0].p, *np = (const int32_t *)small[1].p, *nd = (const int32_t *)small[2].p,
+                  *bk = (const int32_t *)small[3].p, *dn = (const int32_t *)small[4].p;
     const int32_t *pd = (const int32_t *)st.in(pdus, C * MAXJ * MAXPDU * NF * 4);
     const int32_t *sr = (const int32_t *)st.in(sdu, C * MAXJ * MAXPDU * NS * 4);
     const uint8_t *sd = (const uint8_t *)st.in(sdu_data, C * MAXJ * ROWB);

@@ -255,23 +255,10 @@ extern "C" int tetra_etsi_link_quality(tetra_ctx *ctx, const int8_t *softbits, c
         return tetra_fail(ctx, TETRA_E_INVALID, "too many rows or too long a row for one tetra_etsi_link_quality call");
     Staging st(ctx);
     // the three small host arrays travel as one staged input (six staged inputs in all)
-    const uint32_t *ci = cell_init;
-    const int32_t *nb = nburst, *nk = nblock;
-    std::vector<int32_t> small;
-    const bool hc = !is_device_ptr(cell_init), hb = !is_device_ptr(nburst), hk = !is_device_ptr(nblock);
-    if (hc || hb || hk) {
-        const size_t NG = C / G;
-        small.resize((hc ? NG : 0) + (hb ? C : 0) + (hk ? C : 0));
-        size_t at = 0;
-        if (hc) { memcpy(small.data(), cell_init, NG * 4); at = NG; }
-        if (hb) memcpy(small.data() + at, nburst, C * 4);
-        if (hk) memcpy(small.data() + at + (hb ? C : 0), nblock, C * 4);
-        const int32_t *d = (const int32_t *)st.in(small.data(), small.size() * 4);
-        if (!d) return st.finish();
-        if (hc) ci = (const uint32_t *)d;
-        if (hb) nb = d + at;
-        if (hk) nk = d + at + (hb ? C : 0);
-    }
+    Staging::Part small[] = {{cell_init, C / G}, {nburst, C}, {nblock, C}};
+    if (!st.pack(small)) return st.finish();
+    const uint32_t *ci = (const uint32_t *)small[0].p;
+    const int32_t *nb = (const int32_t *)small[1].p, *nk = (const int32_t *)small[2].p;
     const int8_t *sb = (const int8_t *)st.in(softbits, C * stride * 2);
     const uint8_t *hd = (const uint8_t *)st.in(hard, C * stride);
     const int32_t *bu = (const int32_t *)st.in(bursts, C * ETSI_MAXB * 2 * 4);

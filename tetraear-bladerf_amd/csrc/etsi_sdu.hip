@@ -447,20 +447,10 @@ extern "C" int tetra_etsi_sdu(tetra_ctx *ctx, const int32_t *nsym, size_t C, siz
     const size_t NG = C / G;
     Staging st(ctx);
     // the small host arrays travel as one staged input (five staged inputs in all)
-    const int32_t *ns = streaming ? nsym : nullptr, *nb = nburst, *nk = nblock, *np = npdu, *kp = keep;
-    struct Small { const int32_t **p; size_t n; } parts[] = {{&ns, C}, {&nb, C}, {&nk, C}, {&np, C * MAXJ}, {&kp, C * MAXB}};
-    std::vector<int32_t> small;
-    for (auto &s : parts)
-        if (*s.p && !is_device_ptr(*s.p)) small.insert(small.end(), *s.p, *s.p + s.n);
-    if (!small.empty()) {
-        const int32_t *d = (const int32_t *)st.in(small.data(), small.size() * 4);
-        if (!d) return st.finish();
-        for (auto &s : parts)
-            if (*s.p && !is_device_ptr(*s.p)) {
-                *s.p = d;
-                d += s.n;
-            }
-    }
+    Staging::Part small[] = {{streaming ? nsym : nullptr, C}, {nburst, C}, {nblock, C}, {npdu, C * MAXJ}, {keep, C * MAXB}};
+    if (!st.pack(small)) return st.finish();
+    const int32_t *ns = (const int32_t *)small[0].p, *nb = (const int32_t *)small[1].p, *nk = (const int32_t *)small[2].p,
+                  *np = (const int32_t *)small[3].p, *kp = (const int32_t *)small[4].p;
     const int32_t *bu = (const int32_t *)st.in(bursts, C * MAXB * 2 * 4);
     const int32_t *bk = (const int32_t *)st.in(blocks, C * MAXJ * 4 * 4);
     const uint8_t *t1 = (const uint8_t *)st.in(type1, C * MAXJ * 268);

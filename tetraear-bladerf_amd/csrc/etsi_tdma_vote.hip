@@ -248,20 +248,10 @@ extern "C" int tetra_etsi_mac_vote_groups(tetra_ctx *ctx, const int32_t *nsym, s
         return tetra_fail(ctx, TETRA_E_INVALID, "too many rows for one tetra_etsi_mac_vote_groups call (%zu)", C);
     const size_t NG = C / G;
     Staging st(ctx);
-    // the two count arrays travel as one staged input when both are the host's (six staged inputs at most)
-    const int32_t *nb = nburst, *nk = nblock;
-    std::vector<int32_t> counts;
-    if (!is_device_ptr(nburst) && !is_device_ptr(nblock)) {
-        counts.resize(2 * C);
-        memcpy(counts.data(), nburst, C * 4);
-        memcpy(counts.data() + C, nblock, C * 4);
-        nb = (const int32_t *)st.in(counts.data(), 2 * C * 4);
-        if (!nb) return st.finish();
-        nk = nb + C;
-    } else {
-        nb = (const int32_t *)st.in(nburst, C * 4);
-        nk = (const int32_t *)st.in(nblock, C * 4);
-    }
+    // the two count arrays travel as one staged input (six staged inputs at most)
+    Staging::Part small[] = {{nburst, C}, {nblock, C}};
+    if (!st.pack(small)) return st.finish();
+    const int32_t *nb = (const int32_t *)small[0].p, *nk = (const int32_t *)small[1].p;
     const int32_t *bu = (const int32_t *)st.in(bursts, C * MAXB * 2 * 4);
     const int32_t *bk = (const int32_t *)st.in(blocks, C * MAXJ * 4 * 4);
     const uint8_t *t1 = (const uint8_t *)st.in(type1, C * MAXJ * 268);

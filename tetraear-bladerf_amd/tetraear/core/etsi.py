@@ -22,6 +22,9 @@ With ``llc=True`` (and ``sdu=True``) tetra_etsi_llc (k_llc_whole, k_llc_done) fo
 LLC PDU -- type, sequence bits, the frame check sequence, the TL-SDU byte-aligned -- and ``link_messages``
 lists the messages whose LLC PDU reads well.
 """
+import dataclasses
+from collections import namedtuple
+
 import numpy as np
 
 from tetraear import _hip
@@ -89,17 +92,58 @@ def acquired_channels(nblock, blocks):
     return np.any(live & (blocks[:, :, 0] == 2) & (blocks[:, :, 1] != 0), axis=1)
 
 
-def run_link_quality(c, soft, hard, origin, G, cells, nb, bursts, nk, blocks, t1):
-    """tetra_etsi_link_quality on host arrays: (bq [C, MAXB, 4], kq [C, MAXJ, 4]), -1 where not written."""
+# What each stage of the chain leaves, as host arrays over C rows in G-row groups (one group a carrier).
+
+
+class LowerMac(namedtuple("LowerMac", "nb bursts nk blocks t1")):
+    """tetra_lmac_etsi*: nb [C], bursts [C, MAXB, 2], nk [C], blocks [C, MAXJ, 4], t1 [C, MAXJ, 268]."""
+    __slots__ = ()
+
+    @classmethod
+    def zeros(cls, C):
+        """The outputs a lower-MAC call over C rows fills."""
+        return cls(np.zeros(C, np.int32), np.zeros((C, _hip.ETSI_MAXB, 2), np.int32), np.zeros(C, np.int32),
+                   np.zeros((C, _hip.ETSI_MAXJ, 4), np.int32), np.zeros((C, _hip.ETSI_MAXJ, 268), np.uint8))
+
+    def ptrs(self):
+        return tuple(_hip.ptr(v) for v in self)
+
+
+class Mac(namedtuple("Mac", "slots npdu pdus keep slots_reported", defaults=(None, True))):
+    """tetra_etsi_mac*: slots [C, MAXB, 4], npdu [C, MAXJ], pdus [C, MAXJ, MAXPDU, 16]; keep [C, MAXB] int32 from
+    the grouped forms (the copy of each burst kept); slots_reported False: the PDU walk alone ran, a fresh
+    timebase per row, and the frames get no tn / fn / mn / slot_flags."""
+    __slots__ = ()
+
+    @classmethod
+    def zeros(cls, C, keep=False):
+        return cls(np.zeros((C, _hip.ETSI_MAXB, _hip.SLOT_FIELDS), np.int32), np.zeros((C, _hip.ETSI_MAXJ), np.int32),
+                   np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.PDU_FIELDS), np.int32),
+                   np.zeros((C, _hip.ETSI_MAXB), np.int32) if keep else None)
+
+
+# tetra_etsi_link_quality: bq [C, MAXB, 4], kq [C, MAXJ, 4], -1 where not written
+LinkQuality = namedtuple("LinkQuality", "bq kq")
+# tetra_etsi_traffic: tq [C, MAXB, 4], -1 where not written, tch [C, MAXB, 432]; has_cell [C] bool: the row was
+# descrambled with a known cell
+Traffic = namedtuple("Traffic", "tq tch has_cell")
+# tetra_etsi_sdu: sdu [C, MAXJ, MAXPDU, 8], sdu_data [C, MAXJ, 40], ndone [C / G], done [C / G, maxd, 13], done_data
+# [C / G, maxd, 512]
+Sdu = namedtuple("Sdu", "sdu sdu_data ndone done done_data")
+# tetra_etsi_llc: llc [C, MAXJ, MAXPDU, 10], tl [C, MAXJ, 40], llc_done [C / G, maxd, 10], tl_done [C / G, maxd, 512]
+Llc = namedtuple("Llc", "llc tl llc_done tl_done")
+
+
+def run_link_quality(c, soft, hard, origin, G, cells, lm):
+    """tetra_etsi_link_quality on host arrays, lm the LowerMac of the rows: LinkQuality."""
     C, stride = hard.shape
     cells = np.ascontiguousarray(cells, np.uint32)
-    bq = np.full((C, _hip.ETSI_MAXB, _hip.LQ_FIELDS), -1, np.int32)
-    kq = np.full((C, _hip.ETSI_MAXJ, _hip.LQ_FIELDS), -1, np.int32)
+    lq = LinkQuality(np.full((C, _hip.ETSI_MAXB, _hip.LQ_FIELDS), -1, np.int32),
+                     np.full((C, _hip.ETSI_MAXJ, _hip.LQ_FIELDS), -1, np.int32))
     c.check(c.lib.tetra_etsi_link_quality(c.handle, _hip.ptr(soft), _hip.ptr(hard), C, stride, origin, G,
-                                          _hip.ptr(cells), _hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk),
-                                          _hip.ptr(blocks), _hip.ptr(t1), _hip.ptr(bq), _hip.ptr(kq)),
+                                          _hip.ptr(cells), *lm.ptrs(), _hip.ptr(lq.bq), _hip.ptr(lq.kq)),
             "tetra_etsi_link_quality")
-    return bq, kq
+    return lq
 
 
 def burst_quality(rec):
@@ -142,17 +186,19 @@ CODEC_WORDS, CODEC_HEADER = 690, 0x6B21
 CODEC_RUNS = ((1, 114), (116, 114), (231, 114), (346, 90))
 
 
-def run_traffic(c, soft, origin, G, cells, nb, bursts, nk, blocks, slots=None, keep=None):
-    """tetra_etsi_traffic on host arrays (soft [C, 2 stride]): (tq [C, MAXB, 4], -1 where not written,
-    tch [C, MAXB, 432])."""
+def run_traffic(c, soft, origin, G, cells, lm, has_cell, mac=None):
+    """tetra_etsi_traffic on host arrays (soft [C, 2 stride]): Traffic.  mac: None, or the Mac whose reported
+    slots (frame 18 never carries traffic) and keep it is given."""
     C, stride = soft.shape[0], soft.shape[1] // 2
     cells = np.ascontiguousarray(cells, np.uint32)
-    tq = np.full((C, _hip.ETSI_MAXB, _hip.TQ_FIELDS), -1, np.int32)
-    tch = np.zeros((C, _hip.ETSI_MAXB, _hip.TCH_BITS), np.int8)
-    c.check(c.lib.tetra_etsi_traffic(c.handle, _hip.ptr(soft), C, stride, origin, G, _hip.ptr(cells), _hip.ptr(nb),
-                                     _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(slots), _hip.ptr(keep),
-                                     _hip.ptr(tq), _hip.ptr(tch)), "tetra_etsi_traffic")
-    return tq, tch
+    tr = Traffic(np.full((C, _hip.ETSI_MAXB, _hip.TQ_FIELDS), -1, np.int32),
+                 np.zeros((C, _hip.ETSI_MAXB, _hip.TCH_BITS), np.int8), has_cell)
+    timed = mac is not None and mac.slots_reported
+    c.check(c.lib.tetra_etsi_traffic(c.handle, _hip.ptr(soft), C, stride, origin, G, _hip.ptr(cells), _hip.ptr(lm.nb),
+                                     _hip.ptr(lm.bursts), _hip.ptr(lm.nk), _hip.ptr(lm.blocks),
+                                     _hip.ptr(mac.slots if timed else None), _hip.ptr(mac.keep if timed else None),
+                                     _hip.ptr(tr.tq), _hip.ptr(tr.tch)), "tetra_etsi_traffic")
+    return tr
 
 
 def traffic_keys(rec, tch, burst_kind, has_cell=True):
@@ -226,21 +272,18 @@ def slot_usage(frames):
 SDU_MAXD = 16   # done records a row (or a wideband carrier's group) can return from one call
 
 
-def run_sdu(c, nsym, G, row_bits, advance, nb, bursts, nk, blocks, t1, npdu, pdus, keep, frag, maxd=SDU_MAXD,
-            gap_slots=_hip.TDMA_EXPIRE):
-    """tetra_etsi_sdu on host arrays, frag [C / G] (_hip.ETSI_FRAG) updated in place: (sdu [C, MAXJ, MAXPDU,
-    8], sdu_data [C, MAXJ, 40], ndone [C / G], done [C / G, maxd, 13], done_data [C / G, maxd, 512])."""
-    C = len(nb)
-    sdu = np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.SDU_FIELDS), np.int32)
-    sdu_data = np.zeros((C, _hip.ETSI_MAXJ, _hip.SDU_ROW), np.uint8)
-    ndone = np.zeros(C // G, np.int32)
-    done = np.zeros((C // G, maxd, _hip.DONE_FIELDS), np.int32)
-    done_data = np.zeros((C // G, maxd, _hip.SDU_MAXBYTES), np.uint8)
-    c.check(c.lib.tetra_etsi_sdu(c.handle, _hip.ptr(nsym), C, G, row_bits, advance, gap_slots, _hip.ptr(nb),
-                                 _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1), _hip.ptr(npdu),
-                                 _hip.ptr(pdus), _hip.ptr(keep), _hip.ptr(sdu), _hip.ptr(sdu_data), _hip.ptr(frag), maxd,
-                                 _hip.ptr(ndone), _hip.ptr(done), _hip.ptr(done_data)), "tetra_etsi_sdu")
-    return sdu, sdu_data, ndone, done, done_data
+def run_sdu(c, nsym, G, row_bits, advance, lm, mac, keep, frag, maxd=SDU_MAXD, gap_slots=_hip.TDMA_EXPIRE):
+    """tetra_etsi_sdu on host arrays behind the Mac's PDU records, frag [C / G] (_hip.ETSI_FRAG) updated in
+    place: Sdu.  keep: the bursts that feed the chains ([C, MAXB] int32), or None with nsym (the streaming form)."""
+    C = len(lm.nb)
+    sd = Sdu(np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.SDU_FIELDS), np.int32),
+             np.zeros((C, _hip.ETSI_MAXJ, _hip.SDU_ROW), np.uint8), np.zeros(C // G, np.int32),
+             np.zeros((C // G, maxd, _hip.DONE_FIELDS), np.int32), np.zeros((C // G, maxd, _hip.SDU_MAXBYTES), np.uint8))
+    c.check(c.lib.tetra_etsi_sdu(c.handle, _hip.ptr(nsym), C, G, row_bits, advance, gap_slots, *lm.ptrs(),
+                                 _hip.ptr(mac.npdu), _hip.ptr(mac.pdus), _hip.ptr(keep), _hip.ptr(sd.sdu),
+                                 _hip.ptr(sd.sdu_data), _hip.ptr(frag), maxd, _hip.ptr(sd.ndone), _hip.ptr(sd.done),
+                                 _hip.ptr(sd.done_data)), "tetra_etsi_sdu")
+    return sd
 
 
 def sdu_keys(rec, row):
@@ -284,20 +327,16 @@ def done_dict(rec, data, block):
             "gaps": r[_hip.DONE_GAPS], "block": block, "pdu": r[_hip.DONE_PDU]}
 
 
-def run_llc(c, G, nk, blocks, npdu, pdus, sd):
-    """tetra_etsi_llc on host arrays behind run_sdu, sd = what run_sdu returned: (llc [C, MAXJ, MAXPDU, 10],
-    tl [C, MAXJ, 40], llc_done [C / G, maxd, 10], tl_done [C / G, maxd, 512])."""
-    sdu, sdu_data, ndone, done, done_data = sd
-    C, maxd = len(nk), done.shape[1]
-    llc = np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.LLC_FIELDS), np.int32)
-    tl = np.zeros((C, _hip.ETSI_MAXJ, _hip.SDU_ROW), np.uint8)
-    llc_done = np.zeros((C // G, maxd, _hip.LLC_FIELDS), np.int32)
-    tl_done = np.zeros((C // G, maxd, _hip.SDU_MAXBYTES), np.uint8)
-    c.check(c.lib.tetra_etsi_llc(c.handle, C, G, _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(npdu), _hip.ptr(pdus),
-                                 _hip.ptr(sdu), _hip.ptr(sdu_data), maxd, _hip.ptr(ndone), _hip.ptr(done),
-                                 _hip.ptr(done_data), _hip.ptr(llc), _hip.ptr(tl), _hip.ptr(llc_done), _hip.ptr(tl_done)),
-            "tetra_etsi_llc")
-    return llc, tl, llc_done, tl_done
+def run_llc(c, G, lm, mac, sd):
+    """tetra_etsi_llc on host arrays behind run_sdu's Sdu: Llc."""
+    C, maxd = len(lm.nk), sd.done.shape[1]
+    ll = Llc(np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.LLC_FIELDS), np.int32),
+             np.zeros((C, _hip.ETSI_MAXJ, _hip.SDU_ROW), np.uint8), np.zeros((C // G, maxd, _hip.LLC_FIELDS), np.int32),
+             np.zeros((C // G, maxd, _hip.SDU_MAXBYTES), np.uint8))
+    c.check(c.lib.tetra_etsi_llc(c.handle, C, G, _hip.ptr(lm.nk), _hip.ptr(lm.blocks), _hip.ptr(mac.npdu),
+                                 _hip.ptr(mac.pdus), _hip.ptr(sd.sdu), _hip.ptr(sd.sdu_data), maxd, _hip.ptr(sd.ndone),
+                                 _hip.ptr(sd.done), _hip.ptr(sd.done_data), *(_hip.ptr(v) for v in ll)), "tetra_etsi_llc")
+    return ll
 
 
 # Host-side names, transcribed from EN 300 392-2 (clause 21 the LLC PDU types, clause 18 the MLE protocol
@@ -381,6 +420,199 @@ def link_messages(frames, drop_bad_fcs=True):
     return out
 
 
+# The stages that follow the lower MAC.  timebase: None, "walk" (the PDU walk per row, slots not reported), "mac"
+# (tetra_etsi_mac), "groups" (tetra_etsi_mac_groups) or "vote" (tetra_etsi_mac_vote_groups); vote_cap: the bound of the
+# cell vote's scores, None without one.
+ChainOptions = namedtuple("ChainOptions", "timebase link_quality traffic sdu llc tdma_cap vote_cap")
+
+
+def chain_options(mac=False, timebase=False, link_quality=False, traffic=False, sdu=False, llc=False,
+                  tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, vote_cap=None, grouped=False):
+    """The one place the option rules live: ChainOptions, or ValueError.  timebase: False, True or "vote".
+    grouped False (EtsiLowerMac: rows are channels): the timebase is that of mac=True, the vote on it needs
+    mac=True.  grouped True (wideband: G chunk rows a carrier): mac=True alone is the PDU walk, timebase=True
+    merges the rows and implies it, and sdu=True needs both.  vote_cap: None unless the cells are voted on."""
+    if timebase not in (False, True, "vote"):
+        raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
+    if timebase == "vote" and not (mac or grouped):
+        raise ValueError("timebase_vote=True chooses the timebase of mac=True")
+    if sdu and not (mac and (timebase or not grouped)):
+        raise ValueError("sdu=True reads the PDU records of mac=True" +
+                         (" and the keep of timebase=True or 'vote'" if grouped else ""))
+    if llc and not sdu:
+        raise ValueError("llc=True reads the TM-SDUs of mac=True, sdu=True")
+    if timebase == "vote" and int(tdma_cap) <= 0:
+        raise ValueError(f"tdma_cap ({tdma_cap}) must be positive")
+    if vote_cap is not None and int(vote_cap) <= 0:
+        raise ValueError(f"vote_cap ({vote_cap}) must be positive")
+    if grouped:
+        variant = "vote" if timebase == "vote" else "groups" if timebase else "walk" if mac else None
+    else:
+        variant = None if not mac else "vote" if timebase == "vote" else "mac"
+    return ChainOptions(variant, bool(link_quality), bool(traffic), bool(sdu), bool(llc), int(tdma_cap),
+                        None if vote_cap is None else int(vote_cap))
+
+
+class Geometry(namedtuple("Geometry", "G row_bits tol_bits advance", defaults=(1, 0, 32, None))):
+    """How the rows of a call lie: G rows a group, row r of a group starting r row_bits after the group's first,
+    copies of a burst within tol_bits of each other, and the group's stream moving on by ``advance`` bits after
+    the call.  advance None: every row is a channel's own stream (G = 1), which moves on by its chunk's length."""
+    __slots__ = ()
+
+
+@dataclasses.dataclass
+class Carried:
+    """What a stream carries from call to call, one element a group, updated in place (None: a fresh stream):
+    the timebases ([C / G] ETSI_TDMA), the scores they gathered (int32, timebase "vote") and the fragment chains
+    (ETSI_FRAG, sdu)."""
+    tdma: np.ndarray = None
+    tdma_score: np.ndarray = None
+    frag: np.ndarray = None
+    walked: np.ndarray = None   # [C / G], 72 kHz samples of this call's rows: the bursts up to there fed the chains before
+
+
+def run_mac(c, nsym, lm, tdma=None):
+    """tetra_etsi_mac on the lower MAC's outputs, tdma [C] in/out (None: a new stream per row): Mac."""
+    C = len(lm.nb)
+    tdma = np.zeros(C, _hip.ETSI_TDMA) if tdma is None else tdma
+    mac = Mac.zeros(C)
+    c.check(c.lib.tetra_etsi_mac(c.handle, _hip.ptr(nsym), C, *lm.ptrs(), _hip.ptr(tdma), _hip.ptr(mac.slots),
+                                 _hip.ptr(mac.npdu), _hip.ptr(mac.pdus)), "tetra_etsi_mac")
+    return mac
+
+
+def run_mac_groups(c, nsym, geo, advance, cap, lm, lq, tdma, score):
+    """tetra_etsi_mac_groups, or with lq (the rows' LinkQuality) tetra_etsi_mac_vote_groups with the scores
+    score [C / G] bounded by cap: (Mac with keep, the call's ballots [C / G, 4] or None); tdma, score in/out."""
+    C = len(lm.nb)
+    mac = Mac.zeros(C, keep=True)
+    where = (c.handle, _hip.ptr(nsym), C, geo.G, geo.row_bits, geo.tol_bits, advance)
+    outs = tuple(_hip.ptr(v) for v in (mac.keep, mac.slots, mac.npdu, mac.pdus))
+    if lq is None:
+        c.check(c.lib.tetra_etsi_mac_groups(*where, *lm.ptrs(), _hip.ptr(tdma), *outs), "tetra_etsi_mac_groups")
+        return mac, None
+    votes = np.zeros((C // geo.G, _hip.TV_FIELDS), np.int32)
+    c.check(c.lib.tetra_etsi_mac_vote_groups(*where, cap, *lm.ptrs(), _hip.ptr(lq.bq), _hip.ptr(lq.kq), _hip.ptr(tdma),
+                                             _hip.ptr(score), *outs, _hip.ptr(votes)), "tetra_etsi_mac_vote_groups")
+    return mac, votes
+
+
+def run_mac_vote_rows(c, nsym, cap, lm, lq, tdma, score):
+    """tetra_etsi_mac_vote_groups over rows that are each a channel's own stream (G = 1, row_bits = 0): advance
+    is one value a call, so the channels of one chunk length go together, advance = 2 max(nsym - 1, 0), and
+    the in/out arrays are scattered back.  (Mac without keep: one row a group, nothing to choose; ballots [C, 4])."""
+    C = len(lm.nb)
+    mac, votes = Mac.zeros(C), np.zeros((C, _hip.TV_FIELDS), np.int32)
+    for n in np.unique(nsym):
+        idx = np.flatnonzero(nsym == n)
+        if len(idx) == C:
+            part, pv = run_mac_groups(c, nsym, Geometry(), 2 * max(int(n) - 1, 0), cap, lm, lq, tdma, score)
+            return part._replace(keep=None), pv
+        ns_i, tdma_i, score_i = (np.ascontiguousarray(v[idx]) for v in (nsym, tdma, score))
+        part, pv = run_mac_groups(c, ns_i, Geometry(), 2 * max(int(n) - 1, 0), cap,
+                                  LowerMac(*(np.ascontiguousarray(v[idx]) for v in lm)),
+                                  LinkQuality(*(np.ascontiguousarray(v[idx]) for v in lq)), tdma_i, score_i)
+        for dst, src in zip((tdma, score, mac.slots, mac.npdu, mac.pdus, votes),
+                            (tdma_i, score_i, part.slots, part.npdu, part.pdus, pv)):
+            dst[idx] = src
+    return mac, votes
+
+
+def run_chain(c, opt, geo, soft, hard, nsym, origin, cells, has_cell, lm, carried):
+    """The chain behind a lower-MAC call, the one place its order lives: link quality -> MAC -> traffic -> SDU ->
+    LLC -> frames.  soft [C, 2 stride] / hard [C, stride]: the rows the call read, intact, their first bit at
+    ``origin``; nsym [C]; cells [C / G]: the inits they were descrambled with; has_cell [C] bool; lm: the call's
+    LowerMac; carried: Carried, updated in place.  Returns (frames per row, Mac or None, Sdu or None, the vote's
+    ballots or None).  What each stage reads: link quality runs for its keys or for the vote's weights; traffic
+    is given the slots and keep of a MAC call that reports them; the SDU call feeds the bursts the grouped MAC
+    call kept (less those before ``carried.walked``, in 72 kHz samples, which the previous buffer fed), or with
+    rows that are streams of their own every burst of nsym; LLC reads the SDU call's records."""
+    C, G = len(lm.nb), geo.G
+    lq = mac = tr = sd = ll = votes = None
+    if opt.link_quality or opt.timebase == "vote":
+        lq = run_link_quality(c, soft, hard, origin, G, cells, lm)
+    if opt.timebase == "walk":
+        mac = run_mac(c, nsym, lm)._replace(slots_reported=False)
+    elif opt.timebase:
+        if carried.tdma is None:
+            carried.tdma = np.zeros(C // G, _hip.ETSI_TDMA)
+        if opt.timebase == "vote" and carried.tdma_score is None:
+            carried.tdma_score = np.zeros(C // G, np.int32)
+        if opt.timebase == "mac":
+            mac = run_mac(c, nsym, lm, carried.tdma)
+        elif opt.timebase == "vote" and geo.advance is None:   # rows that are streams of their own
+            assert G == 1 and geo.row_bits == 0
+            mac, votes = run_mac_vote_rows(c, nsym, opt.tdma_cap, lm, lq, carried.tdma, carried.tdma_score)
+        else:   # "groups", or "vote" with the link-quality records
+            assert geo.advance is not None, "the grouped MAC calls take the call's advance"
+            mac, votes = run_mac_groups(c, nsym, geo, geo.advance, opt.tdma_cap, lm, lq if opt.timebase == "vote" else None,
+                                        carried.tdma, carried.tdma_score)
+    if opt.traffic:
+        tr = run_traffic(c, soft, origin, G, cells, lm, has_cell, mac)
+    if opt.sdu:
+        if carried.frag is None:
+            carried.frag = np.zeros(C // G, _hip.ETSI_FRAG)
+        fed = mac.keep
+        if fed is not None and carried.walked is not None:   # the carried tail's bursts were fed from the previous buffer
+            sample = 2 * ((np.arange(C) % G)[:, None] * geo.row_bits + lm.bursts[:, :, 0])
+            fed = np.ascontiguousarray(fed * (sample > np.repeat(carried.walked, G)[:, None]), np.int32)
+        sd = run_sdu(c, nsym if fed is None else None, G, geo.row_bits, geo.advance or 0, lm, mac, fed, carried.frag)
+        if opt.llc:
+            ll = run_llc(c, G, lm, mac, sd)
+    return build_frames(lm, mac, lq if opt.link_quality else None, tr, sd, ll, G), mac, sd, votes
+
+
+def build_frames(lm, mac=None, lq=None, tr=None, sd=None, ll=None, G=1):
+    """The frame dicts of every row from the stages' records (None: the stage did not run), sd and ll over groups
+    of G rows.  A Mac whose slots are not reported gives the blocks their pdus and the frames no tn / fn / mn /
+    slot_flags."""
+    nb, bursts, nk, blocks, t1 = lm
+    out = []
+    for ch in range(len(nb)):
+        frames = []
+        for b in range(int(nb[ch])):
+            start, kind = int(bursts[ch, b, 0]), int(bursts[ch, b, 1])
+            blks = []
+            for j in range(int(nk[ch])):
+                if blocks[ch, j, 2] != b:
+                    continue
+                k = int(blocks[ch, j, 0])
+                blks.append({"channel": BLOCK_NAMES[k], "crc_ok": bool(blocks[ch, j, 1]),
+                             "bits": t1[ch, j, :KIND_N1[k]].copy(), "block": int(blocks[ch, j, 3])})
+                if mac is not None:
+                    n = int(mac.npdu[ch, j])
+                    blks[-1].update(npdu=n, pdus=[pdu_dict(r) for r in mac.pdus[ch, j, :min(n, _hip.ETSI_MAXPDU)]])
+                    if sd is not None:
+                        for q, p in enumerate(blks[-1]["pdus"]):
+                            p.update(sdu_keys(sd.sdu[ch, j, q], sd.sdu_data[ch, j]))
+                            if ll is not None:
+                                p["llc"] = llc_keys(ll.llc[ch, j, q], ll.tl[ch, j, int(sd.sdu[ch, j, q, _hip.SDU_BYTE]):])
+                if lq is not None:
+                    blks[-1].update(block_quality(lq.kq[ch, j], k))
+            frames.append({"position": start, "burst": BURST_NAMES[kind], "burst_kind": kind,
+                           "timeslot": (start // 510) % 4, "blocks": blks,
+                           "crc_ok": all(x["crc_ok"] for x in blks)})
+            if mac is not None and mac.slots_reported:
+                tn, fn, mn, fl = (int(v) for v in mac.slots[ch, b])
+                known = tn != 0
+                frames[-1].update(tn=tn if known else None, fn=fn if known else None, mn=mn if known else None,
+                                  slot_flags=fl)
+            if lq is not None:
+                frames[-1].update(burst_quality(lq.bq[ch, b]))
+            if tr is not None:
+                frames[-1].update(traffic_keys(tr.tq[ch, b], tr.tch[ch, b], kind, bool(tr.has_cell[ch])))
+        out.append(frames)
+    if sd is not None:   # a finished chain goes to the frame of the burst that held its MAC-END
+        for g in range(len(nb) // G):
+            for i in range(min(int(sd.ndone[g]), sd.done.shape[1])):
+                row, b = int(sd.done[g, i, _hip.DONE_ROW]), int(sd.done[g, i, _hip.DONE_BURST])
+                blk = int(blocks[row, int(sd.done[g, i, _hip.DONE_BLOCK]), 3])
+                out[row][b].setdefault("sdus", []).append(done_dict(sd.done[g, i], sd.done_data[g, i], blk))
+                if ll is not None:
+                    out[row][b]["sdus"][-1]["llc"] = llc_keys(ll.llc_done[g, i], ll.tl_done[g, i])
+    return out
+
+
 class EtsiLowerMac:
     """Lower MAC of the ETSI chain.  With a cell (mcc, mnc, colour_code) every channel is
     descrambled with it.  Without one the receiver acquires the cell itself: each chunk's BSCH
@@ -446,27 +678,16 @@ class EtsiLowerMac:
     def __init__(self, mcc=None, mnc=None, colour_code=None, mac=False, link_quality=False, vote=False,
                  vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, timebase_vote=False,
                  tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False, llc=False):
-        self.mac = bool(mac)
-        self.sdu = bool(sdu)
-        if self.sdu and not self.mac:
-            raise ValueError("sdu=True reads the PDU records of mac=True")
-        self.llc = bool(llc)
-        if self.llc and not self.sdu:
-            raise ValueError("llc=True reads the TM-SDUs of mac=True, sdu=True")
-        self.traffic = bool(traffic)
-        self.link_quality = bool(link_quality)
+        self.opt = chain_options(mac, "vote" if timebase_vote else False, link_quality, traffic, sdu, llc, tdma_cap,
+                                 vote_cap if vote else None)
+        self.mac, self.sdu, self.llc, self.traffic = bool(mac), self.opt.sdu, self.opt.llc, self.opt.traffic
+        self.link_quality = self.opt.link_quality
         self.timebase_vote, self.tdma_cap = bool(timebase_vote), int(tdma_cap)
-        if self.timebase_vote and not self.mac:
-            raise ValueError("timebase_vote=True chooses the timebase of mac=True")
-        if self.timebase_vote and self.tdma_cap <= 0:
-            raise ValueError(f"tdma_cap ({tdma_cap}) must be positive")
         self.tdma_votes = None   # [C, 4] int32: the last call's ballots (cast, agreed, outvoted, won)
         self.acquire = mcc is None and mnc is None and colour_code is None
         self.vote, self.vote_cap = bool(vote), int(vote_cap)
         if self.vote and not self.acquire:
             raise ValueError("vote=True chooses among acquired cells: it takes no mcc / mnc / colour_code")
-        if self.vote and self.vote_cap <= 0:
-            raise ValueError(f"vote_cap ({vote_cap}) must be positive")
         self.cell_score = None   # [C] int32: the score each channel's cell has gathered (vote=True)
         self.cell = None if self.acquire else scrambling_init(mcc or 0, mnc or 0, colour_code or 0)
         self.cell_state = None   # [C] scrambling inits of the acquired cells (acquisition mode)
@@ -497,21 +718,6 @@ class EtsiLowerMac:
         return {"dropped": self._frag_last["dropped"].copy(), "orphans": self._frag_last["orphans"].copy(),
                 "lost": self._lost.copy()}
 
-    def _run_sdu(self, c, nsym, nb, bursts, nk, blocks, t1, mac, frag):
-        """tetra_etsi_sdu in its streaming form on the MAC call's records (sdu=True; else None)."""
-        if not self.sdu:
-            return None
-        if frag is None or self._lost is None or len(self._lost) != len(nb):
-            self._lost = np.zeros(len(nb), np.int64)
-        if frag is None:
-            frag = np.zeros(len(nb), _hip.ETSI_FRAG)
-        self._frag_last = frag
-        sd = run_sdu(c, nsym, 1, 0, 0, nb, bursts, nk, blocks, t1, mac[1], mac[2], None, frag)
-        self._lost += np.maximum(sd[2] - SDU_MAXD, 0)
-        if self.llc:   # the LLC records ride behind the SDU call's five arrays
-            sd += run_llc(c, 1, nk, blocks, mac[1], mac[2], sd)
-        return sd
-
     @property
     def cells(self):
         """Per channel (MCC, MNC, colour code) acquired so far, None where no BSCH decoded yet."""
@@ -541,45 +747,20 @@ class EtsiLowerMac:
         hard = np.ascontiguousarray(hard, np.uint8)
         nsym = np.ascontiguousarray(nsym, np.int32)
         C, smax = hard.shape
-        nb = np.zeros(C, np.int32)
-        bursts = np.zeros((C, _hip.ETSI_MAXB, 2), np.int32)
-        nk = np.zeros(C, np.int32)
-        blocks = np.zeros((C, _hip.ETSI_MAXJ, 4), np.int32)
-        t1 = np.zeros((C, _hip.ETSI_MAXJ, 268), np.uint8)
+        lm = LowerMac.zeros(C)
         c = _hip.ctx()
-        if self.acquire and cells is None:
-            if self.cell_state is None or len(self.cell_state) != C:
-                self.cell_state = np.full(C, UNKNOWN_CELL, np.uint32)
-                self.acquired = np.zeros(C, bool)
-            if self.acquired is None or len(self.acquired) != C:   # cell_state handed in from outside
-                self.acquired = np.zeros(C, bool)
-            if self.vote:
-                ngood, agree = np.zeros(C, np.int32), np.zeros(C, np.int32)
-                c.check(c.lib.tetra_lmac_etsi_vote_groups(c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(nsym), C,
-                                                          smax, 1, self.vote_cap, _hip.ptr(self.cell_state),
-                                                          _hip.ptr(self._score(C)), _hip.ptr(ngood), _hip.ptr(agree),
-                                                          _hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks),
-                                                          _hip.ptr(t1)), "tetra_lmac_etsi_vote_groups")
-            else:
-                c.check(c.lib.tetra_lmac_etsi_acquire(c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(nsym), C, smax,
-                                                      _hip.ptr(self.cell_state), _hip.ptr(nb), _hip.ptr(bursts),
-                                                      _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
-                        "tetra_lmac_etsi_acquire")
-            self.acquired |= acquired_channels(nk, blocks)
-            used = self.cell_state
+        used, acquiring = self._cells_for(c, C, cells)
+        rows = (c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(nsym), C, smax)
+        if acquiring and self.vote:
+            ngood, agree = np.zeros(C, np.int32), np.zeros(C, np.int32)
+            c.check(c.lib.tetra_lmac_etsi_vote_groups(*rows, 1, self.vote_cap, _hip.ptr(used), _hip.ptr(self._score(C)),
+                                                      _hip.ptr(ngood), _hip.ptr(agree), *lm.ptrs()),
+                    "tetra_lmac_etsi_vote_groups")
+        elif acquiring:
+            c.check(c.lib.tetra_lmac_etsi_acquire(*rows, _hip.ptr(used), *lm.ptrs()), "tetra_lmac_etsi_acquire")
         else:
-            cells = np.full(C, self.cell if self.cell is not None else UNKNOWN_CELL, np.uint32) if cells is None \
-                else np.ascontiguousarray(cells, np.uint32)
-            c.check(c.lib.tetra_etsi_set_cells(c.handle, _hip.ptr(cells), C), "tetra_etsi_set_cells")
-            c.check(c.lib.tetra_lmac_etsi(c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(nsym), C, smax,
-                                          _hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
-                    "tetra_lmac_etsi")
-            used = cells
-        lq = self._run_quality(c, soft, hard, 0, used, nb, bursts, nk, blocks, t1)
-        mac = self._run_mac(c, C, nsym, nb, bursts, nk, blocks, t1, None, lq)
-        tr = self._run_traffic(c, soft, 0, used, nb, bursts, nk, blocks, mac, used is self.cell_state)
-        sd = self._run_sdu(c, nsym, nb, bursts, nk, blocks, t1, mac, None)
-        return self._frames(C, nb, bursts, nk, blocks, t1, mac, lq if self.link_quality else None, tr, sd)
+            c.check(c.lib.tetra_lmac_etsi(*rows, *lm.ptrs()), "tetra_lmac_etsi")
+        return self._chain(c, soft, hard, nsym, 0, used, acquiring, lm, Carried(), False)
 
     def _score(self, C):
         """cell_score for C channels (vote=True): zeros when new or of another length."""
@@ -587,89 +768,38 @@ class EtsiLowerMac:
             self.cell_score = np.zeros(C, np.int32)
         return self.cell_score
 
-    def _run_quality(self, c, soft, hard, origin, cells, nb, bursts, nk, blocks, t1):
-        """tetra_etsi_link_quality on the rows the lower-MAC call read (link_quality=True or
-        timebase_vote=True; else None): (bq, kq).  cells [C]: the inits the rows were descrambled with."""
-        if not (self.link_quality or self.timebase_vote):
-            return None
-        return run_link_quality(c, soft, hard, origin, 1, cells, nb, bursts, nk, blocks, t1)
-
-    def _run_traffic(self, c, soft, origin, cells, nb, bursts, nk, blocks, mac, acquiring):
-        """tetra_etsi_traffic on the rows the lower-MAC call read (traffic=True; else None): (tq, tch,
-        has_cell [C]).  mac: None or the MAC call's (slots, npdu, pdus); acquiring: the cells are the
-        acquisition state, so a channel has one only once a BSCH decoded."""
-        if not self.traffic:
-            return None
-        tq, tch = run_traffic(c, soft, origin, 1, cells, nb, bursts, nk, blocks, None if mac is None else mac[0])
-        return tq, tch, self.acquired.copy() if acquiring else np.ones(len(nb), bool)
-
-    def _run_mac(self, c, C, nsym, nb, bursts, nk, blocks, t1, tdma, lq=None, score=None):
-        """tetra_etsi_mac on the lower MAC's outputs (mac=True; else None): (slots, npdu, pdus).
-        tdma None: a new stream per channel.  timebase_vote=True: tetra_etsi_mac_vote_groups with the
-        call's link-quality records lq and the scores score [C] (None: zeros) instead."""
-        if not self.mac:
-            return None
-        if tdma is None:
-            tdma = np.zeros(C, _hip.ETSI_TDMA)
-        slots = np.zeros((C, _hip.ETSI_MAXB, _hip.SLOT_FIELDS), np.int32)
-        npdu = np.zeros((C, _hip.ETSI_MAXJ), np.int32)
-        pdus = np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.PDU_FIELDS), np.int32)
-        if self.timebase_vote:
-            score = np.zeros(C, np.int32) if score is None else score
-            self.tdma_votes = np.zeros((C, _hip.TV_FIELDS), np.int32)
-            keep = np.zeros((C, _hip.ETSI_MAXB), np.int32)   # one row a group: a row's bursts are a slot apart
-            for n in np.unique(nsym):   # advance is one value a call: the channels of one chunk length together
-                idx = np.flatnonzero(nsym == n)
-                every = len(idx) == C
-                a = [v if every else np.ascontiguousarray(v[idx])
-                     for v in (nsym, nb, bursts, nk, blocks, t1, lq[0], lq[1], tdma, score, keep, slots, npdu, pdus,
-                               self.tdma_votes)]
-                c.check(c.lib.tetra_etsi_mac_vote_groups(c.handle, _hip.ptr(a[0]), len(idx), 1, 0, 32,
-                                                         2 * max(int(n) - 1, 0), self.tdma_cap,
-                                                         *[_hip.ptr(v) for v in a[1:]]), "tetra_etsi_mac_vote_groups")
-                if not every:
-                    for dst, src in zip((tdma, score, slots, npdu, pdus, self.tdma_votes),
-                                        (a[8], a[9], a[11], a[12], a[13], a[14])):
-                        dst[idx] = src
-            return slots, npdu, pdus
-        c.check(c.lib.tetra_etsi_mac(c.handle, _hip.ptr(nsym), C, _hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk),
-                                     _hip.ptr(blocks), _hip.ptr(t1), _hip.ptr(tdma), _hip.ptr(slots), _hip.ptr(npdu),
-                                     _hip.ptr(pdus)), "tetra_etsi_mac")
-        return slots, npdu, pdus
-
-    def _run_stream(self, c, C, nb, bursts, nk, blocks, t1, cells, stream):
-        """tetra_lmac_etsi_stream over stream = (soft rows, hard rows, nsym, stride, lead[, next soft
-        rows, next hard rows]), with the receiver's cell handling (acquisition state or configured
-        cells) as decode_batch's.  Returns the inits the rows were descrambled with."""
+    def _cells_for(self, c, C, cells):
+        """The cells a lower-MAC call over C channels descrambles with: (the acquisition state, made anew when
+        it is missing or of another length, True) in acquisition mode without given ``cells``; else (the given
+        or configured cells, set on the device, False)."""
         if self.acquire and cells is None:
             if self.cell_state is None or len(self.cell_state) != C:
                 self.cell_state = np.full(C, UNKNOWN_CELL, np.uint32)
                 self.acquired = np.zeros(C, bool)
             if self.acquired is None or len(self.acquired) != C:   # cell_state handed in from outside
                 self.acquired = np.zeros(C, bool)
-            ci = _hip.ptr(self.cell_state)
-        else:
-            cells = np.full(C, self.cell if self.cell is not None else UNKNOWN_CELL, np.uint32) if cells is None \
-                else np.ascontiguousarray(cells, np.uint32)
-            c.check(c.lib.tetra_etsi_set_cells(c.handle, _hip.ptr(cells), C), "tetra_etsi_set_cells")
-            ci = None
-        srow, hrow, ns, stride, lead = stream[:5]
-        nsrow, nhrow = stream[5:] if len(stream) > 5 else (srow, hrow)
-        if self.vote and ci is not None:
-            c.check(c.lib.tetra_lmac_etsi_stream_vote(c.handle, _hip.ptr(srow), _hip.ptr(hrow), _hip.ptr(ns), C, stride,
-                                                      _hip.ptr(lead), _hip.ptr(nsrow), _hip.ptr(nhrow), self.vote_cap,
-                                                      ci, _hip.ptr(self._score(C)), None, _hip.ptr(nb),
-                                                      _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
-                    "tetra_lmac_etsi_stream_vote")
-        else:
-            c.check(c.lib.tetra_lmac_etsi_stream(c.handle, _hip.ptr(srow), _hip.ptr(hrow), _hip.ptr(ns), C, stride,
-                                                 _hip.ptr(lead), _hip.ptr(nsrow), _hip.ptr(nhrow), ci, _hip.ptr(nb),
-                                                 _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1)),
-                    "tetra_lmac_etsi_stream")
-        if ci is not None:
-            self.acquired |= acquired_channels(nk, blocks)
-            return self.cell_state
-        return cells
+            return self.cell_state, True
+        cells = np.full(C, self.cell if self.cell is not None else UNKNOWN_CELL, np.uint32) if cells is None \
+            else np.ascontiguousarray(cells, np.uint32)
+        c.check(c.lib.tetra_etsi_set_cells(c.handle, _hip.ptr(cells), C), "tetra_etsi_set_cells")
+        return cells, False
+
+    def _chain(self, c, soft, hard, nsym, origin, used, acquiring, lm, carried, stream):
+        """run_chain behind a lower-MAC call (one row a channel) and the receiver's bookkeeping of it: the
+        channels that acquired a cell, the vote's ballots, the fragment statistics."""
+        C = len(lm.nb)
+        if acquiring:
+            self.acquired |= acquired_channels(lm.nk, lm.blocks)
+        has_cell = self.acquired.copy() if acquiring else np.ones(C, bool)
+        frames, _, sd, votes = run_chain(c, self.opt, Geometry(), soft, hard, nsym, origin, used, has_cell, lm, carried)
+        if votes is not None:
+            self.tdma_votes = votes
+        if sd is not None:   # (decode_batch's fragment state is not carried; its statistics are that call's)
+            if not stream or self._lost is None or len(self._lost) != C:
+                self._lost = np.zeros(C, np.int64)
+            self._frag_last = carried.frag
+            self._lost += np.maximum(sd.ndone - SDU_MAXD, 0)
+        return frames
 
     def decode_stream(self, soft, hard, nsym, cells=None):
         """decode_batch for consecutive chunks of C continuous streams (EtsiStream.demod rows):
@@ -694,86 +824,35 @@ class EtsiLowerMac:
             self._alt = None
         srow, hrow, lead = self._rows
         stride = hrow.shape[1]
-        # the quality and traffic passes read the rows after the call
+        # the quality and traffic passes read the rows after the call: the tails then go to the other set of
+        # rows, and these stay as the call read them
         intact = self.link_quality or self.timebase_vote or self.traffic
         if intact and self._alt is None:
             self._alt = (np.zeros_like(srow), np.zeros_like(hrow))
         hrow[:, R:R + smax] = hard
         srow[:, 2 * R:2 * R + 2 * smax] = soft
-        nb = np.zeros(C, np.int32)
-        bursts = np.zeros((C, _hip.ETSI_MAXB, 2), np.int32)
-        nk = np.zeros(C, np.int32)
-        blocks = np.zeros((C, _hip.ETSI_MAXJ, 4), np.int32)
-        t1 = np.zeros((C, _hip.ETSI_MAXJ, 268), np.uint8)
-        # link_quality: the tails go to the other rows, these stay as the call read them
-        nxt = self._alt if intact else ()
-        used = self._run_stream(_hip.ctx(), C, nb, bursts, nk, blocks, t1, cells,
-                                (srow, hrow, nsym, stride, lead) + tuple(nxt))
-        lq = self._run_quality(_hip.ctx(), srow, hrow, 2 * R, used, nb, bursts, nk, blocks, t1)
+        nsrow, nhrow = self._alt if intact else (srow, hrow)
+        lm = LowerMac.zeros(C)
+        c = _hip.ctx()
+        used, acquiring = self._cells_for(c, C, cells)
+        rows = (c.handle, _hip.ptr(srow), _hip.ptr(hrow), _hip.ptr(nsym), C, stride, _hip.ptr(lead), _hip.ptr(nsrow),
+                _hip.ptr(nhrow))
+        if acquiring and self.vote:
+            c.check(c.lib.tetra_lmac_etsi_stream_vote(*rows, self.vote_cap, _hip.ptr(used), _hip.ptr(self._score(C)),
+                                                      None, *lm.ptrs()), "tetra_lmac_etsi_stream_vote")
+        else:
+            c.check(c.lib.tetra_lmac_etsi_stream(*rows, _hip.ptr(used) if acquiring else None, *lm.ptrs()),
+                    "tetra_lmac_etsi_stream")
         if intact:
-            self._rows, self._alt = (nxt[0], nxt[1], lead), (srow, hrow)
-        if self.mac and (self._tdma is None or len(self._tdma) != C):
-            self._tdma = np.zeros(C, _hip.ETSI_TDMA)
-            self.tdma_score = None
-        if self.timebase_vote and self.tdma_score is None:
-            self.tdma_score = np.zeros(C, np.int32)
-        mac = self._run_mac(_hip.ctx(), C, nsym, nb, bursts, nk, blocks, t1, self._tdma, lq, self.tdma_score)
-        tr = self._run_traffic(_hip.ctx(), srow, 2 * R, used, nb, bursts, nk, blocks, mac, used is self.cell_state)
-        if self.sdu and (self._frag is None or len(self._frag) != C):
-            self._frag = np.zeros(C, _hip.ETSI_FRAG)
-        sd = self._run_sdu(_hip.ctx(), nsym, nb, bursts, nk, blocks, t1, mac, self._frag)
-        return self._frames(C, nb, bursts, nk, blocks, t1, mac, lq if self.link_quality else None, tr, sd)
-
-    @staticmethod
-    def _frames(C, nb, bursts, nk, blocks, t1, mac=None, lq=None, tr=None, sd=None, G=1):
-        """mac: None, or tetra_etsi_mac's (slots, npdu, pdus) for the same call; lq: None, or
-        tetra_etsi_link_quality's (bq, kq); tr: None, or tetra_etsi_traffic's (tq, tch, has_cell [C]); sd:
-        None, or tetra_etsi_sdu's (sdu, sdu_data, ndone, done, done_data) over groups of G rows, with
-        tetra_etsi_llc's (llc, tl, llc_done, tl_done) behind them when llc=True."""
-        out = []
-        for ch in range(C):
-            frames = []
-            for b in range(int(nb[ch])):
-                start, kind = int(bursts[ch, b, 0]), int(bursts[ch, b, 1])
-                blks = []
-                for j in range(int(nk[ch])):
-                    if blocks[ch, j, 2] != b:
-                        continue
-                    k = int(blocks[ch, j, 0])
-                    blks.append({"channel": BLOCK_NAMES[k], "crc_ok": bool(blocks[ch, j, 1]),
-                                 "bits": t1[ch, j, :KIND_N1[k]].copy(), "block": int(blocks[ch, j, 3])})
-                    if mac is not None:
-                        n = int(mac[1][ch, j])
-                        blks[-1].update(npdu=n, pdus=[pdu_dict(r) for r in mac[2][ch, j, :min(n, _hip.ETSI_MAXPDU)]])
-                        if sd is not None:
-                            for q, p in enumerate(blks[-1]["pdus"]):
-                                p.update(sdu_keys(sd[0][ch, j, q], sd[1][ch, j]))
-                                if len(sd) > 5:
-                                    p["llc"] = llc_keys(sd[5][ch, j, q], sd[6][ch, j, int(sd[0][ch, j, q, _hip.SDU_BYTE]):])
-                    if lq is not None:
-                        blks[-1].update(block_quality(lq[1][ch, j], k))
-                frames.append({"position": start, "burst": BURST_NAMES[kind], "burst_kind": kind,
-                               "timeslot": (start // 510) % 4, "blocks": blks,
-                               "crc_ok": all(x["crc_ok"] for x in blks)})
-                if mac is not None:
-                    tn, fn, mn, fl = (int(v) for v in mac[0][ch, b])
-                    known = tn != 0
-                    frames[-1].update(tn=tn if known else None, fn=fn if known else None, mn=mn if known else None,
-                                      slot_flags=fl)
-                if lq is not None:
-                    frames[-1].update(burst_quality(lq[0][ch, b]))
-                if tr is not None:
-                    frames[-1].update(traffic_keys(tr[0][ch, b], tr[1][ch, b], kind, bool(tr[2][ch])))
-            out.append(frames)
-        if sd is not None:   # a finished chain goes to the frame of the burst that held its MAC-END
-            for g in range(C // G):
-                for i in range(min(int(sd[2][g]), sd[3].shape[1])):
-                    row, b = int(sd[3][g, i, _hip.DONE_ROW]), int(sd[3][g, i, _hip.DONE_BURST])
-                    blk = int(blocks[row, int(sd[3][g, i, _hip.DONE_BLOCK]), 3])
-                    out[row][b].setdefault("sdus", []).append(done_dict(sd[3][g, i], sd[4][g, i], blk))
-                    if len(sd) > 5:
-                        out[row][b]["sdus"][-1]["llc"] = llc_keys(sd[7][g, i], sd[8][g, i])
-        return out
+            self._rows, self._alt = (nsrow, nhrow, lead), (srow, hrow)
+        if self._tdma is not None and len(self._tdma) != C:
+            self._tdma = self.tdma_score = None
+        if self._frag is not None and len(self._frag) != C:
+            self._frag = None
+        carried = Carried(self._tdma, self.tdma_score, self._frag)
+        frames = self._chain(c, srow, hrow, nsym, 2 * R, used, acquiring, lm, carried, True)
+        self._tdma, self.tdma_score, self._frag = carried.tdma, carried.tdma_score, carried.frag
+        return frames
 
     def decode(self, symbols, soft_bits=None, stream=True):
         """One chunk of hard dibit symbols (process() output in etsi mode carries soft_bits).

@@ -13,6 +13,7 @@ oracle/wideband.py is the float64 specification the tests hold it to.
 """
 import collections
 import ctypes
+import dataclasses
 import functools
 import os
 
@@ -20,6 +21,7 @@ import numpy as np
 from scipy import signal as _design
 
 from tetraear import _hip
+from tetraear.core.etsi import Carried, Geometry, LowerMac, cell_of, chain_options, run_chain
 from tetraear.signal.etsi import etsi_plan, rrc
 
 FS_WB = 20e6
@@ -160,6 +162,19 @@ def _capture(x):
     return np.ascontiguousarray(x, np.complex64), _hip.TETRA_CF32
 
 
+@dataclasses.dataclass
+class CarrierState(Carried):
+    """What the wideband chain carries per carrier from buffer to buffer beside the Carried timebases, scores
+    and fragment chains ([M] each, updated in place; a fresh one is a new stream per carrier): the acquisition's
+    cell_state (scrambling inits; None: the cells are given), acquired (bool: the carrier had a cell before
+    the call) and cell_score (int32; None: no vote), and ``advance``, the bits a carrier's stream moves on by
+    after the call."""
+    cell_state: np.ndarray = None
+    acquired: np.ndarray = None
+    cell_score: np.ndarray = None
+    advance: int = 0
+
+
 class WidebandReceiver:
     """Channeliser + per-carrier ETSI demod (timing, decision) for host or device arrays.  Every
     method that takes a capture x takes it as [Nw] complex or as [Nw, 2] int16 (SC16, scaled 1/32768 on
@@ -268,8 +283,8 @@ class WidebandReceiver:
         llc=True (needs sdu=True, else ValueError): one tetra_etsi_llc call over the same groups; every pdu
         dict and every entry of ``sdus`` gains ``llc`` (core/etsi.py llc_keys; link_messages() lists the
         messages whose LLC PDU reads well)."""
-        return self._decode(x, np.asarray(cells, np.uint32), None, mac, timebase, tol, link_quality=link_quality,
-                            tdma_cap=tdma_cap, traffic=traffic, sdu=sdu, llc=llc)[0]
+        opt = chain_options(mac, timebase, link_quality, traffic, sdu, llc, tdma_cap, grouped=True)
+        return self._decode(x, np.asarray(cells, np.uint32), opt, tol, CarrierState())[0]
 
     def decode_acquire(self, x, cell_init, mac=False, timebase=False, tol=64, link_quality=False, score=None,
                        vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT,
@@ -297,120 +312,51 @@ class WidebandReceiver:
                                       score.shape == (self.plan.M,) and score.flags["C_CONTIGUOUS"]):
             raise ValueError(f"score must be a C-contiguous int32 array of {self.plan.M} (it is updated in place)")
         had = state != 3 if acquired is None else np.asarray(acquired, bool)
-        frames, ngood = self._decode(x, None, state, mac, timebase, tol, link_quality=link_quality, score=score,
-                                     vote_cap=vote_cap, tdma_cap=tdma_cap, traffic=traffic, acquired=had, sdu=sdu,
-                                     llc=llc)
+        opt = chain_options(mac, timebase, link_quality, traffic, sdu, llc, tdma_cap,
+                            None if score is None else vote_cap, grouped=True)
+        frames, ngood = self._decode(x, None, opt, tol, CarrierState(cell_state=state, acquired=had, cell_score=score))
         return frames, state, ngood
 
-    def _decode(self, x, cells, state, mac, timebase=False, tol=64, tdma=None, advance=0, link_quality=False,
-                score=None, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_score=None,
-                tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, acquired=None, sdu=False, frag=None,
-                walked=None, llc=False):
-        """The chain behind decode (cells [M]) and decode_acquire (state [M], updated in place; score [M]
-        int32 or None, likewise: the vote): (frames, ngood or None).  timebase: tdma [M] ETSI_TDMA (in/out; None: new streams), whose bit0
-        moves on by ``advance`` bits after the call (WidebandStream).  timebase="vote": tdma_score [M] int32
-        (in/out; None: zeros) beside it, scores bounded by tdma_cap.  traffic: tetra_etsi_traffic after
-        the MAC call; acquired [M] bool: the carriers that had a cell before the call (acquisition).
-        sdu: tetra_etsi_sdu after the MAC call with its keep; frag [M] ETSI_FRAG (in/out; None: new
-        streams), whose bit0 moves on by ``advance`` too; walked [M] (72 kHz samples of this buffer, or
-        None): a carrier's bursts up to there were walked from the previous buffer and feed nothing now.
-        llc: tetra_etsi_llc after the SDU call, over the same groups."""
-        from tetraear.core.etsi import EtsiLowerMac, run_link_quality, run_llc, run_sdu, run_traffic
-        if timebase not in (False, True, "vote"):
-            raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
-        if sdu and not (mac and timebase):
-            raise ValueError("sdu=True reads the PDU records of mac=True and the keep of timebase=True or 'vote'")
-        if llc and not sdu:
-            raise ValueError("llc=True reads the TM-SDUs of sdu=True")
-        if timebase and (self.m2 % 2 or tol % 2 or tol < 0):
+    def _decode(self, x, cells, opt, tol, st):
+        """The chain behind decode (cells [M]; st.cell_state None) and decode_acquire (st.cell_state [M], updated
+        in place, and st.cell_score [M] int32 or None, likewise: the vote): (frames, ngood or None).  opt: the
+        ChainOptions; st: the CarrierState, updated in place -- a fresh one a new stream per carrier."""
+        if opt.timebase in ("groups", "vote") and (self.m2 % 2 or tol % 2 or tol < 0):
             raise ValueError(f"timebase=True works in bits: m2 ({self.m2}) and tol ({tol}) must be even")
-        if timebase == "vote" and int(tdma_cap) <= 0:
-            raise ValueError(f"tdma_cap ({tdma_cap}) must be positive")
         hard, soft, _, ns = self.demod(x)
         M, nchunk, sm = hard.shape
         C = M * nchunk
-        nb = np.zeros(C, np.int32)
-        bursts = np.zeros((C, _hip.ETSI_MAXB, 2), np.int32)
-        nk = np.zeros(C, np.int32)
-        blocks = np.zeros((C, _hip.ETSI_MAXJ, 4), np.int32)
-        t1 = np.zeros((C, _hip.ETSI_MAXJ, 268), np.uint8)
+        soft, hard, ns = soft.reshape(C, -1), hard.reshape(C, -1), np.ascontiguousarray(ns.reshape(-1))
+        lm = LowerMac.zeros(C)
         c = _hip.ctx()
-        rows = (_hip.ptr(soft.reshape(C, -1)), _hip.ptr(hard.reshape(C, -1)), _hip.ptr(ns.reshape(-1)), C, sm)
-        outs = (_hip.ptr(nb), _hip.ptr(bursts), _hip.ptr(nk), _hip.ptr(blocks), _hip.ptr(t1))
-        ngood = None
-        if state is None:
+        rows = (c.handle, _hip.ptr(soft), _hip.ptr(hard), _hip.ptr(ns), C, sm)
+        ngood, has = None, np.ones(M, bool)
+        if st.cell_state is None:
             cc = np.ascontiguousarray(np.repeat(cells, nchunk))
             c.check(c.lib.tetra_etsi_set_cells(c.handle, _hip.ptr(cc), C), "tetra_etsi_set_cells")
-            c.check(c.lib.tetra_lmac_etsi(c.handle, *rows, *outs), "tetra_lmac_etsi")
+            c.check(c.lib.tetra_lmac_etsi(*rows, *lm.ptrs()), "tetra_lmac_etsi")
         else:
-            ngood = np.zeros(M, np.int32)
-            if score is not None:
+            cells, ngood = st.cell_state, np.zeros(M, np.int32)
+            if st.cell_score is not None:
                 agree = np.zeros(M, np.int32)
-                c.check(c.lib.tetra_lmac_etsi_vote_groups(c.handle, *rows, nchunk, int(vote_cap), _hip.ptr(state),
-                                                          _hip.ptr(score), _hip.ptr(ngood), _hip.ptr(agree), *outs),
-                        "tetra_lmac_etsi_vote_groups")
+                c.check(c.lib.tetra_lmac_etsi_vote_groups(*rows, nchunk, opt.vote_cap, _hip.ptr(cells),
+                                                          _hip.ptr(st.cell_score), _hip.ptr(ngood), _hip.ptr(agree),
+                                                          *lm.ptrs()), "tetra_lmac_etsi_vote_groups")
             else:
-                c.check(c.lib.tetra_lmac_etsi_acquire_groups(c.handle, *rows, nchunk, _hip.ptr(state),
-                                                             _hip.ptr(ngood), *outs),
+                c.check(c.lib.tetra_lmac_etsi_acquire_groups(*rows, nchunk, _hip.ptr(cells), _hip.ptr(ngood), *lm.ptrs()),
                         "tetra_lmac_etsi_acquire_groups")
-        pdus = lq = tr = sd = None
-        if link_quality or timebase == "vote":   # the rows are intact (origin 0); carrier k's rows with its (acquired) cell
-            lq = run_link_quality(c, soft.reshape(C, -1), hard.reshape(C, -1), 0, nchunk,
-                                  cells if state is None else state, nb, bursts, nk, blocks, t1)
-        if timebase:   # merge and timebase per carrier on the device
-            tdma = np.zeros(M, _hip.ETSI_TDMA) if tdma is None else tdma
-            keep = np.zeros((C, _hip.ETSI_MAXB), np.int32)
-            slots = np.zeros((C, _hip.ETSI_MAXB, _hip.SLOT_FIELDS), np.int32)
-            npdu = np.zeros((C, _hip.ETSI_MAXJ), np.int32)
-            recs = np.zeros((C, _hip.ETSI_MAXJ, _hip.ETSI_MAXPDU, _hip.PDU_FIELDS), np.int32)
-            nsf = np.ascontiguousarray(ns.reshape(-1))
-            if timebase == "vote":   # the weights and the copies' quality from the link-quality records
-                tdma_score = np.zeros(M, np.int32) if tdma_score is None else tdma_score
-                self.tvote = np.zeros((M, _hip.TV_FIELDS), np.int32)
-                c.check(c.lib.tetra_etsi_mac_vote_groups(c.handle, _hip.ptr(nsf), C, nchunk, self.m2 // 2, tol // 2,
-                                                         advance, int(tdma_cap), *outs[:4], _hip.ptr(t1),
-                                                         _hip.ptr(lq[0]), _hip.ptr(lq[1]), _hip.ptr(tdma),
-                                                         _hip.ptr(tdma_score), _hip.ptr(keep), _hip.ptr(slots),
-                                                         _hip.ptr(npdu), _hip.ptr(recs), _hip.ptr(self.tvote)),
-                        "tetra_etsi_mac_vote_groups")
-            else:
-                c.check(c.lib.tetra_etsi_mac_groups(c.handle, _hip.ptr(nsf), C, nchunk, self.m2 // 2, tol // 2, advance,
-                                                    *outs[:4], _hip.ptr(t1), _hip.ptr(tdma), _hip.ptr(keep),
-                                                    _hip.ptr(slots), _hip.ptr(npdu), _hip.ptr(recs)),
-                        "tetra_etsi_mac_groups")
-            if traffic:
-                tr = run_traffic(c, soft.reshape(C, -1), 0, nchunk, cells if state is None else state, nb, bursts, nk,
-                                 blocks, slots, keep)
-            if sdu:
-                fed = keep
-                if walked is not None:   # the carried tail's bursts were walked from the previous buffer
-                    sample = (np.arange(C) % nchunk)[:, None] * self.m2 + 2 * bursts[:, :, 0]
-                    fed = np.ascontiguousarray(keep * (sample > np.repeat(walked, nchunk)[:, None]), np.int32)
-                frag = np.zeros(M, _hip.ETSI_FRAG) if frag is None else frag
-                sd = run_sdu(c, None, nchunk, self.m2 // 2, advance, nb, bursts, nk, blocks, t1, npdu, recs, fed, frag)
-                self.frag_stats = {"dropped": frag["dropped"].copy(), "orphans": frag["orphans"].copy(),
-                                   "lost": np.maximum(sd[2].astype(np.int64) - sd[3].shape[1], 0)}
-                if llc:
-                    sd += run_llc(c, nchunk, nk, blocks, npdu, recs, sd)
-            keep = keep.astype(bool)
-            pdus = (slots, npdu, recs)
+            has = (ngood > 0) | st.acquired
+        frames, mac, sd, votes = run_chain(c, opt, Geometry(nchunk, self.m2 // 2, tol // 2, st.advance), soft, hard, ns,
+                                           0, cells, np.repeat(has, nchunk), lm, st)
+        if votes is not None:
+            self.tvote = votes
+        if sd is not None:
+            self.frag_stats = {"dropped": st.frag["dropped"].copy(), "orphans": st.frag["orphans"].copy(),
+                               "lost": np.maximum(sd.ndone.astype(np.int64) - sd.done.shape[1], 0)}
+        if mac is not None and mac.keep is not None:   # merged on the device
+            keep = mac.keep.astype(bool)
         else:
-            keep, _ = merge_chunks(nb, bursts, nk, blocks, M, nchunk, self.m2, tol)
-        if mac and not timebase:   # the PDU walk is per block; a fresh timebase per row, its slots not reported
-            pdus = EtsiLowerMac(mac=True)._run_mac(c, C, np.ascontiguousarray(ns.reshape(-1)), nb, bursts, nk, blocks,
-                                                  t1, None)
-        if traffic:
-            if tr is None:
-                tr = run_traffic(c, soft.reshape(C, -1), 0, nchunk, cells if state is None else state, nb, bursts, nk,
-                                 blocks)
-            has = np.ones(M, bool) if state is None else (ngood > 0) | acquired
-            tr += (np.repeat(has, nchunk),)
-        frames = EtsiLowerMac._frames(C, nb, bursts, nk, blocks, t1, pdus, lq if link_quality else None, tr, sd, nchunk)
-        if mac and not timebase:
-            for fr in frames:
-                for f in fr:
-                    for key in ("tn", "fn", "mn", "slot_flags"):
-                        del f[key]
+            keep, _ = merge_chunks(lm.nb, lm.bursts, lm.nk, lm.blocks, M, nchunk, self.m2, tol)
         out = [[] for _ in range(M)]
         for ch in range(C):
             for b, f in enumerate(frames[ch]):
@@ -472,21 +418,13 @@ class WidebandStream:
     def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False, timebase=False,
                  link_quality=False, vote=False, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT,
                  tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False, llc=False):
-        if timebase not in (False, True, "vote"):
-            raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
-        self.traffic = bool(traffic)
-        self.sdu = bool(sdu)
-        if self.sdu and not (mac and timebase):
-            raise ValueError("sdu=True reads the PDU records of mac=True and the keep of timebase=True or 'vote'")
-        self.llc = bool(llc)
-        if self.llc and not self.sdu:
-            raise ValueError("llc=True reads the TM-SDUs of sdu=True")
+        self.opt = chain_options(mac, timebase, link_quality, traffic, sdu, llc, tdma_cap, vote_cap if vote else None,
+                                 grouped=True)
+        self.traffic, self.sdu, self.llc = self.opt.traffic, self.opt.sdu, self.opt.llc
+        self.link_quality = self.opt.link_quality
         self.rx = WidebandReceiver(fs, M, m2, oversample)
         self.acquire, self.mac, self.timebase = cells is None, bool(mac), bool(timebase)
         self.tdma_vote, self.tdma_cap = timebase == "vote", int(tdma_cap)
-        if self.tdma_vote and self.tdma_cap <= 0:
-            raise ValueError(f"tdma_cap ({tdma_cap}) must be positive")
-        self.link_quality = bool(link_quality)
         self.vote, self.vote_cap = bool(vote), int(vote_cap)
         if self.vote and not self.acquire:
             raise ValueError("vote=True chooses among acquired cells: it takes no given cells")
@@ -504,7 +442,6 @@ class WidebandStream:
         code) acquired so far, None where no BSCH decoded yet."""
         if not self.acquire:
             return self._cells
-        from tetraear.core.etsi import cell_of
         return [cell_of(v) if a else None for v, a in zip(self.cell_state, self.acquired)]
 
     @property
@@ -541,16 +478,15 @@ class WidebandStream:
 
     def _decode_buffer(self, buf, advance=0):
         if self.timebase:
-            state = np.array(self.cell_state, np.uint32) if self.acquire else None
-            frames, ngood = self.rx._decode(buf, self._cells, state, True, "vote" if self.tdma_vote else True, 64,
-                                            self.tdma, advance, link_quality=self.link_quality,
-                                            score=self.cell_score, vote_cap=self.vote_cap,
-                                            tdma_score=self.tdma_score, tdma_cap=self.tdma_cap, traffic=self.traffic,
-                                            acquired=self.acquired, sdu=self.sdu, frag=self.frag,
-                                            walked=self.last - self.y0 + self.tol if self.sdu else None,
-                                            llc=self.llc)
+            # the stream's attributes as they are now (one assigned from outside counts); cell_state a new array a
+            # buffer, so that one read before the call stays as it was
+            st = CarrierState(self.tdma, self.tdma_score, self.frag, self.last - self.y0 + self.tol if self.sdu else None,
+                              np.array(self.cell_state, np.uint32) if self.acquire else None, self.acquired,
+                              self.cell_score, advance)
+            frames, ngood = self.rx._decode(buf, self._cells, self.opt, 64, st)
+            self.tdma, self.tdma_score, self.frag = st.tdma, st.tdma_score, st.frag
             if self.acquire:
-                self.cell_state = state
+                self.cell_state = st.cell_state
                 self.acquired |= ngood > 0
             if self.sdu:
                 self.lost_sdus += self.rx.frag_stats["lost"]
