@@ -797,7 +797,8 @@ int tetra_etsi_mac_vote_groups(tetra_ctx *ctx, const int32_t *nsym, size_t C, si
  * 128), NZERO = the count of tch_i == 0.  The chain's sign convention is kept: positive means bit 0.
  *
  * Without the AACH a FULL slot is a candidate: a control burst lost to noise looks the same.  WSUM and
- * the timebase are what a caller gates on.
+ * the timebase are what a caller gates on; tetra_etsi_assign (below) adds what the control channel
+ * announced about the carrier and timeslot.
  *
  * C == 0, stride == 0, G == 0, C % G != 0, origin_bits < 0 or a NULL required array: TETRA_E_INVALID,
  * nothing written.  Host or device pointers; with device pointers the call enqueues one kernel on the
@@ -993,6 +994,126 @@ int tetra_etsi_llc(tetra_ctx *ctx, size_t C, size_t G, const int32_t *nblock, co
                    const int32_t *done /*[C/G][maxd][13]*/, const uint8_t *done_data /*[C/G][maxd][512]*/,
                    int32_t *llc /*[C][MAXJ][MAXPDU][10]*/, uint8_t *tl /*[C][MAXJ][40]*/,
                    int32_t *llc_done /*[C/G][maxd][10]*/, uint8_t *tl_done /*[C/G][maxd][512]*/);
+
+/* Channel allocations followed per carrier (a new symbol of ABI version 2; nothing existing changed
+ * shape): the network announces traffic channels in clear on the control channel, and tetra_etsi_sdu
+ * already reads the channel allocation element of every MAC-RESOURCE / MAC-END.  tetra_etsi_assign lists
+ * those announcements with the carrier they name (Part A) and keeps, per carrier and timeslot, who was
+ * assigned there and since when (Part B), so that a traffic candidate of tetra_etsi_traffic can be told
+ * from noise by what the control channel said about it.  It runs after tetra_etsi_sdu on the same rows:
+ * nburst / bursts / nblock / blocks / npdu / pdus / keep as given to it, sdu / ndone / done as it left
+ * them, slots from the MAC call, tq from tetra_etsi_traffic.  All exact integers, restated in
+ * tests/_etsi_assign_model.py.
+ *
+ * Transcribed from EN 300 392-2 and NOT pinned against a conformance vector: the carrier
+ * numbering arithmetic below -- bands of 100 MHz, carriers of 25 kHz, the offsets 0 / +6.25 / -6.25 /
+ * +12.5 kHz -- and the element layout of §5.24.  The records carry the raw fields, so a correction is a
+ * change to this table and the model's.
+ *
+ * Geometry is tetra_etsi_sdu's: G rows a group (a carrier), row i of a group starting row_bits after row
+ * i - 1, the live bursts (b < nburst clamped to 0..MAXB) in the order (pos, row, b), pos = i row_bits +
+ * start bit, p = bit0 + pos (int64).  A burst is kept when keep is NULL or keep[c][b] != 0.  G == 1,
+ * row_bits == 0 and keep == NULL is the streaming form: bit0 advances by 2 max(nsym[c] - 1, 0) (nsym
+ * required); otherwise by `advance` (nsym not read).
+ *
+ * Carrier keys.  row_key [C / G] int32: the group's downlink carrier frequency in units of 6.25 kHz
+ * (Hz / 6250); a negative key means unknown; row_key NULL means every key is -1.  Of a key >= 0, o = key &
+ * 3 is its frequency offset in these units, 0 -> 0, 1 -> +1, 2 -> +2, 3 -> -1; base = key - offset, band =
+ * base / 16000.  The target key of an allocation with carrier number n:
+ *   ELEMS bit 3 clear   band 16000 + 4 n + offset, band and offset those of the carrier that sent it; -1 if
+ *                       that carrier's key is unknown
+ *   ELEMS bit 3 set     ext_band 16000 + 4 n + d, ext_band the 4-bit band and d from the 2-bit offset field
+ *                       of the extended bits: 0 -> 0, 1 -> +1, 2 -> -1, 3 -> +2
+ * Duplex spacing and reverse operation are carried in EXT and not used: only the downlink is followed.
+ *
+ * Part A, events.  nev [C / G] (fully written) counts a group's events; ev [C / G][maxe][TETRA_AE_FIELDS]
+ * holds the first maxe in walk order, the rest is not written (maxe == 0: ev may be NULL).  The walk visits
+ * the group's kept bursts in order; of each burst the blocks j < nblock[c] (clamped to 0..MAXJ) ascending
+ * with blocks[c][j] burst index == b, crc_ok != 0 and kind SCH/F, SCH/HD or BSCH; of each block the PDUs q <
+ * min(npdu[c][j], MAXPDU) ascending.  A PDU is an event when its sdu record has ELEMS bit 2 set and STATUS
+ * == TETRA_SDU_OK and its PDU KIND is MAC-RESOURCE or MAC-END.  The record:
+ *   ROW, BURST, BLOCK, PDU   c, b, j, q;  KIND the PDU kind
+ *   HEAD        the 10 bits allocation type 2, timeslot assigned 4, up/downlink 2, CLCH 1, cell change 1
+ *   CARRIER     the carrier number;  EXT the 10 extended bits, -1 without them;  TARGET the target key
+ *   P_LO, P_HI  the burst's stream bit p, its low and high 32 bits
+ *   TN, FN      of the burst's slots row; 0 when slots is NULL or the slot unknown
+ *   SSI, ADDR_TYPE, AUX   a MAC-RESOURCE's own; a MAC-END's from the first of the group's first min(max(
+ *               ndone[g], 0), maxd) done records whose ROW / BURST / BLOCK / PDU name it, -1 each if none
+ *
+ * Part B, the follower.  state [C / G] (in/out; all zero = a new stream) holds bit0, the counters expired
+ * and released, and one entry per timeslot 1..4.  A recorded event (one of the first min(nev, maxe) of its
+ * group) applies to target group t when TARGET == row_key[t] >= 0, its up/downlink field is 1 or 3
+ * (downlink, or both), its timeslot bitmap is not 0, and t is the group that heard it or shared_clock != 0
+ * -- the caller's promise that all groups count one sample clock, as the rows of a wideband capture do.
+ * The time T of an event is its burst's p.  Per target group its applicable events, sorted by (T, source
+ * group, ordinal in the source's list), and its own kept bursts, in their order, are merged by time: an
+ * event at T is handled after every burst with p <= T and before every burst with p > T.
+ *   Event.  For each timeslot n whose bit is set in the bitmap (its most significant bit is timeslot 1):
+ *     an inactive entry becomes active with since = T, nalloc = 0, idle = 0; in every case last = T, nalloc
+ *     += 1, and ssi / addr_type / aux / head become the event's SSI / ADDR_TYPE / AUX / HEAD, src_key the
+ *     key of the carrier that sent it.
+ *   Burst.  A kept burst takes part when slots gives its TN in 1..4 and, with tq given, its tq CLASS is
+ *     not negative.  With d the entry of TN and slots_of(x) = floor((x + 255) / 510):
+ *     1. if d is active and slots_of(p - last) > hold_slots it is freed, expired += 1;
+ *     2. ta [C][MAXB][TETRA_TA_FIELDS] of the burst is written: STATE 1 if d is active, else 0; SSI,
+ *        ADDR_TYPE, AUX, SRC_KEY, NALLOC, IDLE the entry's, AGE = slots_of(p - since) (its low 32 bits); an
+ *        inactive entry reads SSI -1, ADDR_TYPE 0, AUX -1, SRC_KEY -1, NALLOC 0, IDLE 0, AGE 0;
+ *     3. with tq given and d active: CLASS FULL or HALF sets idle = 0 and last = p; CLASS CONTROL on a
+ *        burst whose FN is not 18 does idle += 1, and if then idle > idle_max the entry is freed, released
+ *        += 1.
+ *   Every other live burst -- not kept, TN unknown, slots NULL, or invalid for tetra_etsi_traffic -- reads
+ *   STATE -1 and 0 in the other fields.  Rows past nburst are not written.  A freed entry keeps its other
+ *   fields.  After the walk bit0 advances.
+ *
+ * Limits.  This follows announcements, it is not the AACH: without the AACH or CMCE's D-RELEASE nothing
+ * announces the end of a call, so an allocation is kept alive by repeats (late-entry signalling) and by the
+ * slot still looking like traffic, and ends when the slot visibly returns to decoded control signalling or
+ * when neither was seen for hold_slots.  A carrier lost to noise reads FULL for ever and keeps its entry:
+ * soft_sum, AGE and IDLE are what a caller gates on.  The augmented allocation (STATUS 4), uplink-only
+ * allocations and encrypted PDUs are not followed.  TETRA_ASSIGN_HOLD_DEFAULT and TETRA_ASSIGN_IDLE_DEFAULT
+ * are stated choices, not measurements.
+ *
+ * C == 0, G outside 1..64, C % G != 0, a NULL required array (every one but keep, slots, tq, row_key; nsym
+ * in the streaming form; done when maxd > 0; ev when maxe > 0), row_bits, maxe, maxd, hold_slots or
+ * idle_max < 0, C > 2^24: TETRA_E_INVALID, nothing written.  Host or device pointers; with device pointers
+ * the call enqueues three kernels on the context stream and returns without waiting (no allocation, no
+ * synchronising copy). */
+#define TETRA_ASSIGN_HOLD_DEFAULT 720   /* slots, ten multiframes: a stated choice, not a measurement */
+#define TETRA_ASSIGN_IDLE_DEFAULT 72    /* bursts of a timeslot, four multiframes: a stated choice likewise */
+enum {
+    TETRA_AE_ROW = 0, TETRA_AE_BURST, TETRA_AE_BLOCK, TETRA_AE_PDU, TETRA_AE_KIND, TETRA_AE_HEAD, TETRA_AE_CARRIER,
+    TETRA_AE_EXT, TETRA_AE_TARGET, TETRA_AE_P_LO, TETRA_AE_P_HI, TETRA_AE_TN, TETRA_AE_FN, TETRA_AE_SSI,
+    TETRA_AE_ADDR_TYPE, TETRA_AE_AUX, TETRA_AE_FIELDS = 16
+};
+enum {
+    TETRA_TA_STATE = 0, TETRA_TA_SSI, TETRA_TA_ADDR_TYPE, TETRA_TA_AUX, TETRA_TA_SRC_KEY, TETRA_TA_NALLOC,
+    TETRA_TA_IDLE, TETRA_TA_AGE, TETRA_TA_FIELDS = 8
+};
+typedef struct tetra_etsi_assign_slot {
+    int64_t since;                     /* stream bit of the allocation that made the entry active */
+    int64_t last;                      /* stream bit of the last allocation or traffic burst */
+    int32_t active;
+    int32_t ssi, addr_type, aux;       /* of the last allocation */
+    int32_t src_key;                   /* key of the carrier that sent it */
+    int32_t head;                      /* its 10 head bits */
+    int32_t nalloc;                    /* allocations since the entry became active */
+    int32_t idle;                      /* decoded control bursts since the last traffic burst */
+} tetra_etsi_assign_slot;
+typedef struct tetra_etsi_assign_state {   /* per carrier, carried from call to call; all zero = new stream */
+    int64_t bit0;                      /* stream bit index of this call's position 0 */
+    int32_t expired;                   /* entries freed after hold_slots without a repeat or traffic */
+    int32_t released;                  /* entries freed because the slot returned to control signalling */
+    tetra_etsi_assign_slot slot[4];    /* timeslots 1..4 */
+} tetra_etsi_assign_state;
+int tetra_etsi_assign(tetra_ctx *ctx, const int32_t *nsym, size_t C, size_t G, int64_t row_bits, int64_t advance,
+                      int32_t hold_slots, int32_t idle_max, int32_t shared_clock, const int32_t *nburst,
+                      const int32_t *bursts, const int32_t *nblock, const int32_t *blocks, const int32_t *npdu,
+                      const int32_t *pdus, const int32_t *keep /*[C][MAXB] or NULL*/,
+                      const int32_t *slots /*[C][MAXB][4] or NULL*/, const int32_t *tq /*[C][MAXB][4] or NULL*/,
+                      const int32_t *sdu /*[C][MAXJ][MAXPDU][8]*/, int32_t maxd, const int32_t *ndone /*[C/G]*/,
+                      const int32_t *done /*[C/G][maxd][13]*/, const int32_t *row_key /*[C/G] or NULL*/,
+                      tetra_etsi_assign_state *state /*[C/G] in/out*/, int32_t maxe, int32_t *nev /*[C/G]*/,
+                      int32_t *ev /*[C/G][maxe][16]*/, int32_t *ta /*[C][MAXB][8]*/);
 
 /* The ETSI receiver's AFC mixer on a streaming window: out [C][N] cf32 = iq (cf32 rows ld samples
  * apart) x exp(-j 2 pi f (n0 + n) / fs), n0 = the window's first sample in the capture (frequency_shift's

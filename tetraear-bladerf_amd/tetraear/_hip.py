@@ -111,6 +111,17 @@ ETSI_FRAG = __import__("numpy").dtype([("bit0", "<i8"), ("dropped", "<i4"), ("or
  LLC_FIELDS) = range(11)
 LLC_OK, LLC_NONE, LLC_MALFORMED, LLC_ENCRYPTED, LLC_UNSUPPORTED = range(5)
 FCS_NONE, FCS_GOOD, FCS_BAD = range(3)
+# tetra_etsi_assign (include/tetra_hip.h): the event records, the bursts' ta records, struct tetra_etsi_assign_state;
+# the defaults are stated choices (ten multiframes of slots, four multiframes of a timeslot's bursts)
+ASSIGN_HOLD_DEFAULT, ASSIGN_IDLE_DEFAULT = 720, 72
+(AE_ROW, AE_BURST, AE_BLOCK, AE_PDU, AE_KIND, AE_HEAD, AE_CARRIER, AE_EXT, AE_TARGET, AE_P_LO, AE_P_HI, AE_TN, AE_FN,
+ AE_SSI, AE_ADDR_TYPE, AE_AUX, AE_FIELDS) = range(17)
+TA_STATE, TA_SSI, TA_ADDR_TYPE, TA_AUX, TA_SRC_KEY, TA_NALLOC, TA_IDLE, TA_AGE, TA_FIELDS = range(9)
+ETSI_ASSIGN_SLOT = __import__("numpy").dtype([("since", "<i8"), ("last", "<i8"), ("active", "<i4"), ("ssi", "<i4"),
+                                             ("addr_type", "<i4"), ("aux", "<i4"), ("src_key", "<i4"), ("head", "<i4"),
+                                             ("nalloc", "<i4"), ("idle", "<i4")])
+ETSI_ASSIGN = __import__("numpy").dtype([("bit0", "<i8"), ("expired", "<i4"), ("released", "<i4"),
+                                        ("slot", ETSI_ASSIGN_SLOT, (4,))])
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -197,6 +208,9 @@ def _bind(L):
                                   _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
         "tetra_etsi_llc": (_i32, [_vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp]),
+        "tetra_etsi_assign": (_i32, [_vp, _vp, _sz, _sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp,
+                                     _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
         "tetra_etsi_mix": (_i32, [_vp, _vp, _sz, _sz, _sz, _vp, ctypes.c_double, ctypes.c_int64, _vp]),
         "tetra_etsi_decode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp, _vp]),
         "tetra_etsi_encode_blocks": (_i32, [_vp, _vp, _sz, _i32, _vp, _vp]),

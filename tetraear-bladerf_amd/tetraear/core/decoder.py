@@ -90,7 +90,7 @@ class TetraDecoder:
 
     def __init__(self, key_manager=None, auto_decrypt: bool = True, mode=None, mac: bool = False,
                  link_quality: bool = False, vote: bool = False, timebase_vote: bool = False,
-                 traffic: bool = False, sdu: bool = False, llc: bool = False):
+                 traffic: bool = False, sdu: bool = False, llc: bool = False, follow: bool = False, carrier_hz=None):
         self.SYNC_PATTERN = [0, 1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0,
                              1, 0, 1, 1, 0, 0, 1, 1, 1, 0, 0, 0, 1, 0, 0]
         self.FRAME_LENGTH = 510
@@ -113,6 +113,8 @@ class TetraDecoder:
         self.etsi_sdu = bool(sdu)
         # mode="etsi", mac=True, sdu=True: every TM-SDU read as an LLC PDU (EtsiLowerMac(llc=True))
         self.etsi_llc = bool(llc)
+        # mode="etsi", mac=True, sdu=True: the channel allocations followed (EtsiLowerMac(follow=True, carrier_hz=...))
+        self.etsi_follow, self.etsi_carrier_hz = bool(follow), carrier_hz
 
     # ------------------------------------------------------------------ keys and the reference's rest
     def set_keys(self, keys):
@@ -416,6 +418,7 @@ class TetraDecoder:
             frame.update({k: f[k] for k in ("training_errors", "edge_errors", "soft_sum", "saturated")
                           if k in f})   # EtsiLowerMac(link_quality=True); the blocks carry theirs
             frame.update({k: f[k] for k in ("usage", "traffic") if k in f})   # EtsiLowerMac(traffic=True)
+            frame.update({k: f[k] for k in ("assigned", "assignment", "allocations") if k in f})   # (follow=True)
             while k < len(owner) and owner[k] == i:   # the MAC state advances in block order
                 pdu = self.protocol_parser.mac_state(fields[k], data[k])
                 if pdu is not None:
@@ -479,5 +482,6 @@ class TetraDecoder:
             from tetraear.core.etsi import EtsiLowerMac
             self._etsi = EtsiLowerMac(mac=self.etsi_mac, link_quality=self.etsi_link_quality, vote=self.etsi_vote,
                                       timebase_vote=self.etsi_timebase_vote, traffic=self.etsi_traffic,
-                                      sdu=self.etsi_sdu, llc=self.etsi_llc)
+                                      sdu=self.etsi_sdu, llc=self.etsi_llc, follow=self.etsi_follow,
+                                      carrier_hz=self.etsi_carrier_hz)
         return self._etsi

@@ -21,6 +21,10 @@ finished TM-SDUs for an upper MAC.
 With ``llc=True`` (and ``sdu=True``) tetra_etsi_llc (k_llc_whole, k_llc_done) follows: every TM-SDU is read as an
 LLC PDU -- type, sequence bits, the frame check sequence, the TL-SDU byte-aligned -- and ``link_messages``
 lists the messages whose LLC PDU reads well.
+With ``follow=True`` (and ``sdu=True``) tetra_etsi_assign (k_assign_scan, k_assign_events, k_assign_follow)
+follows: the channel allocations the control channel announces are listed with the carrier they name, and
+every burst says whether its carrier and timeslot were assigned, to whom and since when (``assigned`` /
+``assignment`` / ``allocations``; ``assigned_streams`` lists a carrier's assigned traffic frames).
 """
 import dataclasses
 from collections import namedtuple
@@ -339,6 +343,104 @@ def run_llc(c, G, lm, mac, sd):
     return ll
 
 
+# tetra_etsi_assign: nev [C / G], ev [C / G, maxe, 16], ta [C, MAXB, 8], -1 where not written; row_key [C / G] int32 or None
+Assign = namedtuple("Assign", "nev ev ta row_key")
+ASSIGN_MAXE = 16   # events a row (or a wideband carrier's group) can return from one call
+# The carrier numbering (include/tetra_hip.h, tetra_etsi_assign), transcribed from EN 300 392-2 and NOT pinned
+# against a conformance vector: keys count 6.25 kHz, a band is 100 MHz, a carrier 25 kHz.
+KEY_HZ, KEY_BAND, KEY_CARRIER = 6250, 16000, 4
+KEY_OFFSET = {0: 0, 1: 1, 2: 2, 3: -1}   # a key's two low bits -> its offset from the 25 kHz raster, in keys
+EXT_OFFSET = {0: 0, 1: 1, 2: -1, 3: 2}   # the extended carrier numbering's offset field -> the same
+
+
+def carrier_key(hz):
+    """The key of a downlink carrier frequency: hz / 6250.  ValueError unless hz is a multiple of 6250 Hz."""
+    k = int(round(float(hz) / KEY_HZ))
+    if k < 0 or k * KEY_HZ != float(hz):
+        raise ValueError(f"a carrier frequency is a non-negative multiple of {KEY_HZ} Hz, not {hz!r}")
+    return k
+
+
+def key_hz(key):
+    """The frequency in Hz of a key; None for an unknown (negative) key."""
+    return None if key is None or int(key) < 0 else int(key) * KEY_HZ
+
+
+def allocation_key(ca, own_key):
+    """The key a channel_allocation dict (sdu_keys) names when the carrier with own_key sent it, -1 when it
+    cannot be told: tetra_etsi_assign's TARGET, restated on the host."""
+    if "carrier" not in ca:   # the augmented form stops before the carrier number
+        return -1
+    ext = ca.get("extended")
+    if ext is not None:
+        return ext["band"] * KEY_BAND + KEY_CARRIER * ca["carrier"] + EXT_OFFSET[ext["offset"]]
+    if own_key is None or int(own_key) < 0:
+        return -1
+    off = KEY_OFFSET[int(own_key) & 3]
+    return (int(own_key) - off) // KEY_BAND * KEY_BAND + KEY_CARRIER * ca["carrier"] + off
+
+
+def run_assign(c, nsym, G, row_bits, advance, lm, mac, keep, sd, tq, state, row_key, shared_clock, maxe=ASSIGN_MAXE,
+               hold_slots=_hip.ASSIGN_HOLD_DEFAULT, idle_max=_hip.ASSIGN_IDLE_DEFAULT):
+    """tetra_etsi_assign on host arrays behind run_sdu's Sdu, state [C / G] (_hip.ETSI_ASSIGN) updated in place:
+    Assign.  keep: what run_sdu was given; tq: the traffic call's records or None; row_key [C / G] int32 or None."""
+    C = len(lm.nb)
+    row_key = None if row_key is None else np.ascontiguousarray(row_key, np.int32)
+    asg = Assign(np.zeros(C // G, np.int32), np.full((C // G, maxe, _hip.AE_FIELDS), -1, np.int32),
+                 np.full((C, _hip.ETSI_MAXB, _hip.TA_FIELDS), -1, np.int32), row_key)
+    c.check(c.lib.tetra_etsi_assign(c.handle, _hip.ptr(nsym), C, G, row_bits, advance, hold_slots, idle_max,
+                                    int(bool(shared_clock)), _hip.ptr(lm.nb), _hip.ptr(lm.bursts), _hip.ptr(lm.nk),
+                                    _hip.ptr(lm.blocks), _hip.ptr(mac.npdu), _hip.ptr(mac.pdus), _hip.ptr(keep),
+                                    _hip.ptr(mac.slots), _hip.ptr(tq), _hip.ptr(sd.sdu), sd.done.shape[1], _hip.ptr(sd.ndone),
+                                    _hip.ptr(sd.done), _hip.ptr(row_key), _hip.ptr(state), maxe, _hip.ptr(asg.nev),
+                                    _hip.ptr(asg.ev), _hip.ptr(asg.ta)), "tetra_etsi_assign")
+    return asg
+
+
+def allocation_dict(rec, row_key, block):
+    """One event record of tetra_etsi_assign as an entry of a frame's ``allocations``: the raw fields, ``target_hz``
+    (None when the target cannot be told) and ``target_row`` (the group of this call with that key, else None);
+    ``block`` (the block's index in its burst) and ``pdu`` say where the PDU sat."""
+    r = [int(v) for v in rec]
+    head, ext, target = r[_hip.AE_HEAD], r[_hip.AE_EXT], r[_hip.AE_TARGET]
+    rows = np.flatnonzero(row_key == target) if row_key is not None and target >= 0 else ()
+    d = {"kind": PDU_NAMES[r[_hip.AE_KIND]], "block": block, "pdu": r[_hip.AE_PDU],
+         "allocation_type": (head >> 8) & 3, "timeslot_assigned": (head >> 4) & 15, "updownlink_assigned": (head >> 2) & 3,
+         "clch_permission": (head >> 1) & 1, "cell_change": head & 1, "carrier": r[_hip.AE_CARRIER],
+         "extended": None if ext < 0 else {"band": ext >> 6, "offset": (ext >> 4) & 3, "duplex_spacing": (ext >> 1) & 7,
+                                           "reverse_operation": ext & 1},
+         "target_hz": key_hz(target), "target_row": int(rows[0]) if len(rows) else None,
+         "ssi": None if r[_hip.AE_SSI] < 0 else r[_hip.AE_SSI], "address_type": r[_hip.AE_ADDR_TYPE],
+         "aux": None if r[_hip.AE_AUX] < 0 else r[_hip.AE_AUX]}
+    return d
+
+
+def assignment_keys(rec):
+    """One ta record of tetra_etsi_assign as the keys a frame gains: ``assigned`` (True: the control channel
+    assigned this carrier and timeslot and nothing ended it since; False; None: the burst was not followed -- a
+    copy not kept, no timeslot yet) and ``assignment`` (None, or dict(ssi, address_type, usage_marker, from_hz,
+    age_slots, allocations, idle))."""
+    r = [int(v) for v in rec]
+    if r[_hip.TA_STATE] != 1:
+        return {"assigned": False if r[_hip.TA_STATE] == 0 else None, "assignment": None}
+    at = r[_hip.TA_ADDR_TYPE]
+    return {"assigned": True,
+            "assignment": {"ssi": None if r[_hip.TA_SSI] < 0 else r[_hip.TA_SSI], "address_type": at,
+                           "usage_marker": r[_hip.TA_AUX] if at == 6 else None, "from_hz": key_hz(r[_hip.TA_SRC_KEY]),
+                           "age_slots": r[_hip.TA_AGE], "allocations": r[_hip.TA_NALLOC], "idle": r[_hip.TA_IDLE]}}
+
+
+def assigned_streams(frames):
+    """One carrier's frames (traffic=True, follow=True) -> {tn: [frame, ...]} of its "traffic" and "stolen" frames
+    whose timeslot the control channel assigned (``assigned`` True), in the order given: traffic_streams with
+    the announcement as the gate."""
+    out = {}
+    for f in frames:
+        if f.get("usage") in ("traffic", "stolen") and f.get("assigned") is True:
+            out.setdefault(f.get("tn"), []).append(f)
+    return out
+
+
 # Host-side names, transcribed from EN 300 392-2 (clause 21 the LLC PDU types, clause 18 the MLE protocol
 # discriminator, clause 14 the CMCE downlink PDU types) and NOT pinned against a conformance vector: the
 # device records carry the raw TYPE and HEAD, so a correction is a change to these tables.
@@ -423,15 +525,17 @@ def link_messages(frames, drop_bad_fcs=True):
 # The stages that follow the lower MAC.  timebase: None, "walk" (the PDU walk per row, slots not reported), "mac"
 # (tetra_etsi_mac), "groups" (tetra_etsi_mac_groups) or "vote" (tetra_etsi_mac_vote_groups); vote_cap: the bound of the
 # cell vote's scores, None without one.
-ChainOptions = namedtuple("ChainOptions", "timebase link_quality traffic sdu llc tdma_cap vote_cap")
+ChainOptions = namedtuple("ChainOptions", "timebase link_quality traffic sdu llc tdma_cap vote_cap follow",
+                          defaults=(False,))
 
 
 def chain_options(mac=False, timebase=False, link_quality=False, traffic=False, sdu=False, llc=False,
-                  tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, vote_cap=None, grouped=False):
+                  tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, vote_cap=None, grouped=False, follow=False):
     """The one place the option rules live: ChainOptions, or ValueError.  timebase: False, True or "vote".
     grouped False (EtsiLowerMac: rows are channels): the timebase is that of mac=True, the vote on it needs
     mac=True.  grouped True (wideband: G chunk rows a carrier): mac=True alone is the PDU walk, timebase=True
-    merges the rows and implies it, and sdu=True needs both.  vote_cap: None unless the cells are voted on."""
+    merges the rows and implies it, and sdu=True needs both.  vote_cap: None unless the cells are voted on.
+    follow=True reads the SDU call's records and the MAC call's slots: it needs what sdu=True needs, and sdu=True."""
     if timebase not in (False, True, "vote"):
         raise ValueError(f"timebase={timebase!r}: False, True or 'vote'")
     if timebase == "vote" and not (mac or grouped):
@@ -441,6 +545,9 @@ def chain_options(mac=False, timebase=False, link_quality=False, traffic=False, 
                          (" and the keep of timebase=True or 'vote'" if grouped else ""))
     if llc and not sdu:
         raise ValueError("llc=True reads the TM-SDUs of mac=True, sdu=True")
+    if follow and not sdu:
+        raise ValueError("follow=True reads the channel allocations of mac=True, sdu=True" +
+                         (" on the timebase of timebase=True or 'vote'" if grouped else ""))
     if timebase == "vote" and int(tdma_cap) <= 0:
         raise ValueError(f"tdma_cap ({tdma_cap}) must be positive")
     if vote_cap is not None and int(vote_cap) <= 0:
@@ -450,7 +557,7 @@ def chain_options(mac=False, timebase=False, link_quality=False, traffic=False, 
     else:
         variant = None if not mac else "vote" if timebase == "vote" else "mac"
     return ChainOptions(variant, bool(link_quality), bool(traffic), bool(sdu), bool(llc), int(tdma_cap),
-                        None if vote_cap is None else int(vote_cap))
+                        None if vote_cap is None else int(vote_cap), bool(follow))
 
 
 class Geometry(namedtuple("Geometry", "G row_bits tol_bits advance", defaults=(1, 0, 32, None))):
@@ -463,12 +570,13 @@ class Geometry(namedtuple("Geometry", "G row_bits tol_bits advance", defaults=(1
 @dataclasses.dataclass
 class Carried:
     """What a stream carries from call to call, one element a group, updated in place (None: a fresh stream):
-    the timebases ([C / G] ETSI_TDMA), the scores they gathered (int32, timebase "vote") and the fragment chains
-    (ETSI_FRAG, sdu)."""
+    the timebases ([C / G] ETSI_TDMA), the scores they gathered (int32, timebase "vote"), the fragment chains
+    (ETSI_FRAG, sdu) and the assigned timeslots (ETSI_ASSIGN, follow)."""
     tdma: np.ndarray = None
     tdma_score: np.ndarray = None
     frag: np.ndarray = None
     walked: np.ndarray = None   # [C / G], 72 kHz samples of this call's rows: the bursts up to there fed the chains before
+    assign: np.ndarray = None
 
 
 def run_mac(c, nsym, lm, tdma=None):
@@ -518,17 +626,19 @@ def run_mac_vote_rows(c, nsym, cap, lm, lq, tdma, score):
     return mac, votes
 
 
-def run_chain(c, opt, geo, soft, hard, nsym, origin, cells, has_cell, lm, carried):
+def run_chain(c, opt, geo, soft, hard, nsym, origin, cells, has_cell, lm, carried, row_key=None, shared_clock=False):
     """The chain behind a lower-MAC call, the one place its order lives: link quality -> MAC -> traffic -> SDU ->
-    LLC -> frames.  soft [C, 2 stride] / hard [C, stride]: the rows the call read, intact, their first bit at
+    LLC -> assign -> frames.  soft [C, 2 stride] / hard [C, stride]: the rows the call read, intact, their first bit at
     ``origin``; nsym [C]; cells [C / G]: the inits they were descrambled with; has_cell [C] bool; lm: the call's
     LowerMac; carried: Carried, updated in place.  Returns (frames per row, Mac or None, Sdu or None, the vote's
     ballots or None).  What each stage reads: link quality runs for its keys or for the vote's weights; traffic
     is given the slots and keep of a MAC call that reports them; the SDU call feeds the bursts the grouped MAC
     call kept (less those before ``carried.walked``, in 72 kHz samples, which the previous buffer fed), or with
-    rows that are streams of their own every burst of nsym; LLC reads the SDU call's records."""
+    rows that are streams of their own every burst of nsym; LLC reads the SDU call's records; assign (opt.follow)
+    reads them too, with the keep the SDU call got, the traffic call's records when it ran, and row_key [C / G]
+    (the groups' carrier keys, None: unknown) / shared_clock (the groups count one sample clock)."""
     C, G = len(lm.nb), geo.G
-    lq = mac = tr = sd = ll = votes = None
+    lq = mac = tr = sd = ll = asg = votes = None
     if opt.link_quality or opt.timebase == "vote":
         lq = run_link_quality(c, soft, hard, origin, G, cells, lm)
     if opt.timebase == "walk":
@@ -559,12 +669,17 @@ def run_chain(c, opt, geo, soft, hard, nsym, origin, cells, has_cell, lm, carrie
         sd = run_sdu(c, nsym if fed is None else None, G, geo.row_bits, geo.advance or 0, lm, mac, fed, carried.frag)
         if opt.llc:
             ll = run_llc(c, G, lm, mac, sd)
-    return build_frames(lm, mac, lq if opt.link_quality else None, tr, sd, ll, G), mac, sd, votes
+        if opt.follow:
+            if carried.assign is None:
+                carried.assign = np.zeros(C // G, _hip.ETSI_ASSIGN)
+            asg = run_assign(c, nsym if fed is None else None, G, geo.row_bits, geo.advance or 0, lm, mac, fed, sd,
+                             None if tr is None else tr.tq, carried.assign, row_key, shared_clock)
+    return build_frames(lm, mac, lq if opt.link_quality else None, tr, sd, ll, G, asg), mac, sd, votes
 
 
-def build_frames(lm, mac=None, lq=None, tr=None, sd=None, ll=None, G=1):
-    """The frame dicts of every row from the stages' records (None: the stage did not run), sd and ll over groups
-    of G rows.  A Mac whose slots are not reported gives the blocks their pdus and the frames no tn / fn / mn /
+def build_frames(lm, mac=None, lq=None, tr=None, sd=None, ll=None, G=1, asg=None):
+    """The frame dicts of every row from the stages' records (None: the stage did not run), sd, ll and asg over
+    groups of G rows.  A Mac whose slots are not reported gives the blocks their pdus and the frames no tn / fn / mn /
     slot_flags."""
     nb, bursts, nk, blocks, t1 = lm
     out = []
@@ -601,6 +716,8 @@ def build_frames(lm, mac=None, lq=None, tr=None, sd=None, ll=None, G=1):
                 frames[-1].update(burst_quality(lq.bq[ch, b]))
             if tr is not None:
                 frames[-1].update(traffic_keys(tr.tq[ch, b], tr.tch[ch, b], kind, bool(tr.has_cell[ch])))
+            if asg is not None:
+                frames[-1].update(assignment_keys(asg.ta[ch, b]), allocations=None)
         out.append(frames)
     if sd is not None:   # a finished chain goes to the frame of the burst that held its MAC-END
         for g in range(len(nb) // G):
@@ -610,6 +727,13 @@ def build_frames(lm, mac=None, lq=None, tr=None, sd=None, ll=None, G=1):
                 out[row][b].setdefault("sdus", []).append(done_dict(sd.done[g, i], sd.done_data[g, i], blk))
                 if ll is not None:
                     out[row][b]["sdus"][-1]["llc"] = llc_keys(ll.llc_done[g, i], ll.tl_done[g, i])
+    if asg is not None:   # an allocation goes to the frame of the burst it was heard in
+        for g in range(len(nb) // G):
+            for i in range(min(int(asg.nev[g]), asg.ev.shape[1])):
+                row = int(asg.ev[g, i, _hip.AE_ROW])
+                f = out[row][int(asg.ev[g, i, _hip.AE_BURST])]
+                blk = int(blocks[row, int(asg.ev[g, i, _hip.AE_BLOCK]), 3])
+                f["allocations"] = (f["allocations"] or []) + [allocation_dict(asg.ev[g, i], asg.row_key, blk)]
     return out
 
 
@@ -673,13 +797,31 @@ class EtsiLowerMac:
 
     ``llc=True`` (with ``mac=True, sdu=True``): tetra_etsi_llc runs after the SDU call.  Every pdu dict and
     every entry of ``sdus`` gains ``llc`` (llc_keys): the LLC type, sequence bits, the FCS verdict and the
-    TL-SDU; ``link_messages(frames)`` lists the messages that read well.  Everything else is unchanged."""
+    TL-SDU; ``link_messages(frames)`` lists the messages that read well.  Everything else is unchanged.
+
+    ``follow=True`` (with ``mac=True, sdu=True``): tetra_etsi_assign runs after the SDU / LLC calls.  Every frame
+    gains ``assigned`` (True: the control channel assigned this carrier and timeslot, and neither the hold time
+    nor decoded control signalling ended it; False; None: the burst has no timeslot yet), ``assignment`` (None,
+    or dict(ssi, address_type, usage_marker, from_hz, age_slots, allocations, idle)) and ``allocations`` (None,
+    or the channel allocations heard in the burst, allocation_dict, each with ``target_hz`` / ``target_row``).
+    ``carrier_hz``: the channels' downlink carrier frequencies, one value or one per channel, multiples of 6250
+    Hz; without it every allocation is listed and nothing is assigned.  The channels' streams count their own
+    clocks, so only a carrier's allocations onto itself apply (the wideband chain joins carriers).  This follows
+    announcements, it is not the AACH: a call's end is inferred (``age_slots``, ``idle`` and ``soft_sum`` are what a
+    caller gates on), and the carrier numbering is transcribed from EN 300 392-2, not pinned.  The state is
+    carried like the timebase; ``assign_stats`` counts the entries that expired and that were released.
+    ``assigned_streams(frames)`` lists a carrier's assigned traffic.  Everything else is unchanged."""
 
     def __init__(self, mcc=None, mnc=None, colour_code=None, mac=False, link_quality=False, vote=False,
                  vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, timebase_vote=False,
-                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False, llc=False):
+                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False, llc=False, follow=False,
+                 carrier_hz=None):
         self.opt = chain_options(mac, "vote" if timebase_vote else False, link_quality, traffic, sdu, llc, tdma_cap,
-                                 vote_cap if vote else None)
+                                 vote_cap if vote else None, follow=follow)
+        self.follow = self.opt.follow
+        # the channels' keys: None (unknown), one int for every channel, or one per channel
+        self.carrier_keys = None if carrier_hz is None else carrier_key(carrier_hz) if np.ndim(carrier_hz) == 0 else \
+            np.array([carrier_key(v) for v in carrier_hz], np.int32)
         self.mac, self.sdu, self.llc, self.traffic = bool(mac), self.opt.sdu, self.opt.llc, self.opt.traffic
         self.link_quality = self.opt.link_quality
         self.timebase_vote, self.tdma_cap = bool(timebase_vote), int(tdma_cap)
@@ -706,7 +848,27 @@ class EtsiLowerMac:
         self._frag = None   # [C] tetra_etsi_frag: the carried fragment chains (sdu=True)
         self._frag_last = None   # the state the last call left (decode_batch's is not carried)
         self._lost = None   # [C] completions beyond SDU_MAXD a call, which no frame carries
+        self._assign = None   # [C] tetra_etsi_assign_state: the carried assignments (follow=True)
+        self._assign_last = None   # the state the last call left (decode_batch's is not carried)
 
+    @property
+    def assign_stats(self):
+        """follow=True: dict(expired [C], released [C]) -- assignments that ended after the hold time without
+        a repeat or traffic, and that ended because the slot returned to decoded control signalling -- since
+        the stream began (decode_batch: of that call); None before the first call."""
+        if self._assign_last is None:
+            return None
+        return {"expired": self._assign_last["expired"].copy(), "released": self._assign_last["released"].copy()}
+
+    def _row_keys(self, C):
+        """row_key for a call over C channels, None when no carrier frequency was given."""
+        if self.carrier_keys is None:
+            return None
+        if np.ndim(self.carrier_keys) == 0:
+            return np.full(C, self.carrier_keys, np.int32)
+        if len(self.carrier_keys) != C:
+            raise ValueError(f"carrier_hz names {len(self.carrier_keys)} channels, the call has {C}")
+        return self.carrier_keys
     @property
     def frag_stats(self):
         """sdu=True: dict(dropped [C], orphans [C]) -- chains freed unfinished (expired, superseded,
@@ -791,7 +953,10 @@ class EtsiLowerMac:
         if acquiring:
             self.acquired |= acquired_channels(lm.nk, lm.blocks)
         has_cell = self.acquired.copy() if acquiring else np.ones(C, bool)
-        frames, _, sd, votes = run_chain(c, self.opt, Geometry(), soft, hard, nsym, origin, used, has_cell, lm, carried)
+        frames, _, sd, votes = run_chain(c, self.opt, Geometry(), soft, hard, nsym, origin, used, has_cell, lm, carried,
+                                         self._row_keys(C) if self.follow else None)
+        if self.follow:
+            self._assign_last = carried.assign
         if votes is not None:
             self.tdma_votes = votes
         if sd is not None:   # (decode_batch's fragment state is not carried; its statistics are that call's)
@@ -849,9 +1014,11 @@ class EtsiLowerMac:
             self._tdma = self.tdma_score = None
         if self._frag is not None and len(self._frag) != C:
             self._frag = None
-        carried = Carried(self._tdma, self.tdma_score, self._frag)
+        if self._assign is not None and len(self._assign) != C:
+            self._assign = None
+        carried = Carried(self._tdma, self.tdma_score, self._frag, assign=self._assign)
         frames = self._chain(c, srow, hrow, nsym, 2 * R, used, acquiring, lm, carried, True)
-        self._tdma, self.tdma_score, self._frag = carried.tdma, carried.tdma_score, carried.frag
+        self._tdma, self.tdma_score, self._frag, self._assign = carried.tdma, carried.tdma_score, carried.frag, carried.assign
         return frames
 
     def decode(self, symbols, soft_bits=None, stream=True):

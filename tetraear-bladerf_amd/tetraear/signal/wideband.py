@@ -21,7 +21,7 @@ import numpy as np
 from scipy import signal as _design
 
 from tetraear import _hip
-from tetraear.core.etsi import Carried, Geometry, LowerMac, cell_of, chain_options, run_chain
+from tetraear.core.etsi import Carried, Geometry, LowerMac, carrier_key, cell_of, chain_options, run_chain
 from tetraear.signal.etsi import etsi_plan, rrc
 
 FS_WB = 20e6
@@ -162,6 +162,18 @@ def _capture(x):
     return np.ascontiguousarray(x, np.complex64), _hip.TETRA_CF32
 
 
+def row_keys(plan, center_hz):
+    """follow=True: the carrier key (core/etsi.py carrier_key, Hz / 6250) of every row of the plan.  Row k is FFT
+    bin k of a capture centred on center_hz: carrier_key(center_hz) + 4 (k if k < M / 2 else k - M).  ValueError
+    without center_hz, and unless the rows lie 25 kHz apart exactly (fs / M), as the carrier numbering does."""
+    if center_hz is None:
+        raise ValueError("follow=True maps carrier numbers to rows: it needs center_hz")
+    if plan.fs != 25000.0 * plan.M:
+        raise ValueError(f"follow=True needs rows 25 kHz apart: fs / M is {plan.fs / plan.M} Hz")
+    k = np.arange(plan.M)
+    return (carrier_key(center_hz) + 4 * np.where(k < plan.M // 2, k, k - plan.M)).astype(np.int32)
+
+
 @dataclasses.dataclass
 class CarrierState(Carried):
     """What the wideband chain carries per carrier from buffer to buffer beside the Carried timebases, scores
@@ -173,6 +185,7 @@ class CarrierState(Carried):
     acquired: np.ndarray = None
     cell_score: np.ndarray = None
     advance: int = 0
+    keys: np.ndarray = None   # follow: the carriers' keys (row_keys)
 
 
 class WidebandReceiver:
@@ -186,6 +199,7 @@ class WidebandReceiver:
         self.m2 = m2
         self.tvote = None   # [M, 4] int32: the ballots of the last decode with timebase="vote"
         self.frag_stats = None   # dict(dropped [M], orphans [M]) of the last decode with sdu=True
+        self.assign_stats = None   # dict(expired [M], released [M]) of the last decode with follow=True
 
     def channelize(self, x, n_keep=None):
         """x [Nw] complex64 or [Nw, 2] int16 -> y [M][n_keep] complex64 at 72 kHz."""
@@ -248,7 +262,8 @@ class WidebandReceiver:
 
 
     def decode(self, x, cells, mac=False, timebase=False, tol=64, link_quality=False,
-               tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False, llc=False):
+               tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False, llc=False, follow=False,
+               center_hz=None):
         """x [Nw] -> per carrier the frames decoded from it, each burst once (merge_chunks), in row
         order: demod, then the ETSI lower MAC on every (carrier, chunk) with carrier k's scrambling
         init cells[k].  A frame is the lower MAC's dict (core/etsi.py) plus "chunk" and "sample" (its
@@ -282,13 +297,21 @@ class WidebandReceiver:
         completed beyond the SDU_MAXD (core/etsi.py) a call returns per carrier, which reach no frame.
         llc=True (needs sdu=True, else ValueError): one tetra_etsi_llc call over the same groups; every pdu
         dict and every entry of ``sdus`` gains ``llc`` (core/etsi.py llc_keys; link_messages() lists the
-        messages whose LLC PDU reads well)."""
-        opt = chain_options(mac, timebase, link_quality, traffic, sdu, llc, tdma_cap, grouped=True)
-        return self._decode(x, np.asarray(cells, np.uint32), opt, tol, CarrierState())[0]
+        messages whose LLC PDU reads well).
+        follow=True (needs sdu=True and center_hz, the capture's centre frequency in Hz, else ValueError): one
+        tetra_etsi_assign call over the same groups joins the carriers of the capture -- row k is the carrier at
+        center_hz + 25 kHz x (k if k < M / 2 else k - M), the rows count one sample clock, so a channel
+        allocation heard on one carrier marks the timeslot it names on the row of the carrier it names.  Every
+        frame gains ``assigned`` / ``assignment`` / ``allocations`` as EtsiLowerMac(follow=True)'s frames carry
+        them (``from_hz``: the carrier that announced it; ``target_row``: the row an allocation names);
+        ``assign_stats`` holds expired / released per carrier.  An announcement, not the AACH: see EtsiLowerMac."""
+        opt = chain_options(mac, timebase, link_quality, traffic, sdu, llc, tdma_cap, grouped=True, follow=follow)
+        keys = row_keys(self.plan, center_hz) if opt.follow else None
+        return self._decode(x, np.asarray(cells, np.uint32), opt, tol, CarrierState(keys=keys))[0]
 
     def decode_acquire(self, x, cell_init, mac=False, timebase=False, tol=64, link_quality=False, score=None,
                        vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT, tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT,
-                       traffic=False, acquired=None, sdu=False, llc=False):
+                       traffic=False, acquired=None, sdu=False, llc=False, follow=False, center_hz=None):
         """decode without given cells: cell_init [M] holds each carrier's scrambling init before the
         capture (3 = unknown); every carrier's cell comes from the last CRC-good BSCH over all of its
         chunk rows, and all of its rows are descrambled with it (tetra_lmac_etsi_acquire_groups, G =
@@ -304,7 +327,7 @@ class WidebandReceiver:
         default cell_init[k] == 3 -- reports ``usage`` None (its blocks were descrambled with no cell, so
         a failed CRC says nothing).  The default misreads a carrier whose known cell is all zero (MCC =
         MNC = colour code = 0), which has the init of "unknown": pass ``acquired`` for such a carrier, as
-        WidebandStream does from piece to piece.  sdu=True, llc=True: decode's."""
+        WidebandStream does from piece to piece.  sdu=True, llc=True, follow=True with center_hz: decode's."""
         state = np.array(cell_init, np.uint32)
         if state.shape != (self.plan.M,):
             raise ValueError(f"cell_init holds {state.shape} inits, the receiver has {self.plan.M} carriers")
@@ -313,14 +336,17 @@ class WidebandReceiver:
             raise ValueError(f"score must be a C-contiguous int32 array of {self.plan.M} (it is updated in place)")
         had = state != 3 if acquired is None else np.asarray(acquired, bool)
         opt = chain_options(mac, timebase, link_quality, traffic, sdu, llc, tdma_cap,
-                            None if score is None else vote_cap, grouped=True)
-        frames, ngood = self._decode(x, None, opt, tol, CarrierState(cell_state=state, acquired=had, cell_score=score))
+                            None if score is None else vote_cap, grouped=True, follow=follow)
+        keys = row_keys(self.plan, center_hz) if opt.follow else None
+        frames, ngood = self._decode(x, None, opt, tol, CarrierState(cell_state=state, acquired=had, cell_score=score,
+                                                                    keys=keys))
         return frames, state, ngood
 
     def _decode(self, x, cells, opt, tol, st):
         """The chain behind decode (cells [M]; st.cell_state None) and decode_acquire (st.cell_state [M], updated
         in place, and st.cell_score [M] int32 or None, likewise: the vote): (frames, ngood or None).  opt: the
-        ChainOptions; st: the CarrierState, updated in place -- a fresh one a new stream per carrier."""
+        ChainOptions; st: the CarrierState, updated in place -- a fresh one a new stream per carrier (st.keys [M]:
+        the carriers' keys, row_keys, with opt.follow)."""
         if opt.timebase in ("groups", "vote") and (self.m2 % 2 or tol % 2 or tol < 0):
             raise ValueError(f"timebase=True works in bits: m2 ({self.m2}) and tol ({tol}) must be even")
         hard, soft, _, ns = self.demod(x)
@@ -347,7 +373,9 @@ class WidebandReceiver:
                         "tetra_lmac_etsi_acquire_groups")
             has = (ngood > 0) | st.acquired
         frames, mac, sd, votes = run_chain(c, opt, Geometry(nchunk, self.m2 // 2, tol // 2, st.advance), soft, hard, ns,
-                                           0, cells, np.repeat(has, nchunk), lm, st)
+                                           0, cells, np.repeat(has, nchunk), lm, st, st.keys, True)
+        if opt.follow:
+            self.assign_stats = {"expired": st.assign["expired"].copy(), "released": st.assign["released"].copy()}
         if votes is not None:
             self.tvote = votes
         if sd is not None:
@@ -404,6 +432,10 @@ class WidebandStream:
     the carried tail's bursts, decoded again, feed nothing a second time.  ``frag_stats``: the chains
     dropped and the orphans per carrier since reset().
     ``llc=True`` (with ``sdu=True``): the pdu dicts and the ``sdus`` entries carry ``llc`` (WidebandReceiver.decode).
+    ``follow=True`` (with ``sdu=True`` and ``center_hz``): the frames carry ``assigned`` / ``assignment`` /
+    ``allocations`` (WidebandReceiver.decode); one assignment state per carrier is carried from piece to piece in
+    ``assign`` [M] with the advance of ``tdma`` (reset() clears it), so a call announced in one piece marks the
+    traffic of the next; ``assign_stats``: the entries expired and released per carrier since reset().
     ``vote=True`` (acquisition only): a carrier's cell is chosen by the vote over each buffer's BSCH
     blocks (WidebandReceiver.decode_acquire(score=...)), the score it gathers carried from piece to piece
     in ``cell_score`` and read as ``cell_scores`` (reset() clears it).  A burst in the carried tail is
@@ -417,9 +449,11 @@ class WidebandStream:
 
     def __init__(self, cells=None, fs=FS_WB, M=M_WB, m2=M2_CHUNK, oversample=None, tol=64, mac=False, timebase=False,
                  link_quality=False, vote=False, vote_cap=_hip.TETRA_ETSI_VOTE_CAP_DEFAULT,
-                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False, llc=False):
+                 tdma_cap=_hip.TETRA_TDMA_VOTE_CAP_DEFAULT, traffic=False, sdu=False, llc=False, follow=False,
+                 center_hz=None):
         self.opt = chain_options(mac, timebase, link_quality, traffic, sdu, llc, tdma_cap, vote_cap if vote else None,
-                                 grouped=True)
+                                 grouped=True, follow=follow)
+        self.follow = self.opt.follow
         self.traffic, self.sdu, self.llc = self.opt.traffic, self.opt.sdu, self.opt.llc
         self.link_quality = self.opt.link_quality
         self.rx = WidebandReceiver(fs, M, m2, oversample)
@@ -434,6 +468,7 @@ class WidebandStream:
         p = self.rx.plan
         blocks = int(np.lcm(p.c.down, p.oversample))   # filter-bank blocks per period
         self.per, self.ups, self.M, self.tol = p.D * blocks, p.c.up * blocks // p.c.down, p.M, tol
+        self.keys = row_keys(p, center_hz) if self.follow else None
         self.reset()
 
     @property
@@ -468,6 +503,13 @@ class WidebandStream:
         self.tdma_score = np.zeros(self.M, np.int32) if self.tdma_vote else None   # timebase="vote"
         self.frag = np.zeros(self.M, _hip.ETSI_FRAG) if self.sdu else None   # sdu=True: the fragment chains
         self.lost_sdus = np.zeros(self.M, np.int64)
+        self.assign = np.zeros(self.M, _hip.ETSI_ASSIGN) if self.follow else None   # follow=True: the assigned timeslots
+
+    @property
+    def assign_stats(self):
+        """follow=True: dict(expired [M], released [M]) since reset(); else None."""
+        return None if self.assign is None else {"expired": self.assign["expired"].copy(),
+                                                 "released": self.assign["released"].copy()}
 
     @property
     def frag_stats(self):
@@ -481,10 +523,10 @@ class WidebandStream:
             # the stream's attributes as they are now (one assigned from outside counts); cell_state a new array a
             # buffer, so that one read before the call stays as it was
             st = CarrierState(self.tdma, self.tdma_score, self.frag, self.last - self.y0 + self.tol if self.sdu else None,
-                              np.array(self.cell_state, np.uint32) if self.acquire else None, self.acquired,
-                              self.cell_score, advance)
+                              self.assign, np.array(self.cell_state, np.uint32) if self.acquire else None, self.acquired,
+                              self.cell_score, advance, self.keys)
             frames, ngood = self.rx._decode(buf, self._cells, self.opt, 64, st)
-            self.tdma, self.tdma_score, self.frag = st.tdma, st.tdma_score, st.frag
+            self.tdma, self.tdma_score, self.frag, self.assign = st.tdma, st.tdma_score, st.frag, st.assign
             if self.acquire:
                 self.cell_state = st.cell_state
                 self.acquired |= ngood > 0
@@ -523,6 +565,8 @@ class WidebandStream:
             self.tdma["bit0"] += dy // 2
             if self.sdu:
                 self.frag["bit0"] += dy // 2
+            if self.follow:
+                self.assign["bit0"] += dy // 2
         if n72 >= 16:
             for k, fr in enumerate(self._decode_buffer(buf, dy // 2)):
                 for f in fr:
