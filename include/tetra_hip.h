@@ -491,6 +491,68 @@ int tetra_lmac_etsi_stream(tetra_ctx *ctx, const int8_t *softbits, const uint8_t
                            uint32_t *cell_init, int32_t *nburst, int32_t *bursts, int32_t *nblock, int32_t *blocks,
                            uint8_t *type1);
 
+/* ---------------------------------------------------------------- loss-of-lock monitor (new symbols of ABI
+ * version 2; nothing existing changed shape).  A streaming channel's timing loop, filter history and
+ * lower-MAC tail are carried from chunk to chunk, and nothing in tetra_demod_etsi_stream sets
+ * track.acquired back to 0: after a retune, an SDR sample drop or a signal that went away, the loop is
+ * joined onto stale state, and a slip of about half a symbol cannot be tracked out at all (the block-
+ * Gardner offset is clamped to +-1.5 of the 4 samples a symbol has).  tetra_etsi_lock
+ * judges every chunk from its soft bits and the loop's offset and hands a channel that lost lock back
+ * to acquisition (k_etsi_lock, one launch; tests/_etsi_lock_model.py restates it; no reference
+ * counterpart: the reference demodulates every chunk on its own,
+ * /root/reference/tetraear/signal/processor.py:253-331).
+ *
+ * Call it after tetra_demod_etsi_stream, on that call's softbits, nsym, ostride and track, on the same
+ * context (host or device pointers, as that call takes them; with device pointers it enqueues and
+ * returns without waiting).
+ *
+ * Sums (exact integers).  N = min(max(nsym[c] - 1, 0), ostride) dibits of row c, bytes (s0, s1) each;
+ * a = |s0|, b = |s1| (-128 reads 128), hi = max(a, b), lo = min(a, b).  A dibit with hi < weak counts
+ * in WEAK; every other one adds lo to SMIN and hi to SMAX.  A clean pi/4-DQPSK decision has |s0| =
+ * |s1|, so SMIN / SMAX ("balance") is near 1 in lock and near 0.44 on noise or at a wrong timing phase.
+ * Nothing past byte 2 N of a row is read.
+ *
+ * Rule, per channel.  An all-zero state reads as {searching = 1}: the first chunk of a stream is an
+ * acquisition chunk.  fresh = state.searching on entry; judged = N >= nmin; chunks += 1 always, and an
+ * unjudged chunk changes nothing else.  A judged chunk is bad if 2 WEAK > N, or SMAX == 0, or
+ * (int64) SMIN den < (int64) num SMAX, or railed: |track[c].delta| >= 1.5f, the loop's own clamp (an
+ * exact compare; NaN is not railed).
+ *   good:             searching = 0, bad_run = 0;
+ *   bad and fresh:    track[c].acquired = 0, searching = 1 -- the channel keeps searching, every chunk
+ *                     acquiring afresh as every chunk did before streaming;
+ *   bad, not fresh:   bad_run += 1, and at bad_run >= patience the channel is DROPPED:
+ *                     track[c].acquired = 0, searching = 1, bad_run = 0, relocks += 1.
+ * rec [C][TETRA_LOCK_FIELDS] (fully written): SMIN, SMAX, N, WEAK, the TETRA_LOCK_* flag bits, bad_run
+ * and relocks after the chunk, 0.
+ * TETRA_E_INVALID with nothing written: a NULL softbits, nsym, track, state or rec, C == 0, ostride == 0
+ * or above 2^23 (the sums are 32-bit), C above 2^24, den <= 0, num < 0, patience < 1. */
+typedef struct tetra_etsi_lock_state {
+    int32_t searching;   /* 1: the channel has no lock; the next judged chunk is an acquisition chunk */
+    int32_t bad_run;     /* consecutive bad chunks since the last good one (locked channels) */
+    int32_t relocks;     /* times the channel was dropped */
+    int32_t chunks;      /* calls so far */
+    int32_t reserved[4];
+} tetra_etsi_lock_state;
+enum {
+    TETRA_LOCK_SMIN = 0, TETRA_LOCK_SMAX, TETRA_LOCK_N, TETRA_LOCK_WEAK, TETRA_LOCK_FLAGS, TETRA_LOCK_BAD_RUN,
+    TETRA_LOCK_RELOCKS, TETRA_LOCK_FIELDS = 8
+};
+#define TETRA_LOCK_JUDGED 1      /* N >= nmin */
+#define TETRA_LOCK_BAD 2
+#define TETRA_LOCK_RAILED 4      /* |delta| >= 1.5 after the chunk (reported for unjudged chunks too) */
+#define TETRA_LOCK_FRESH 8       /* the channel was searching on entry */
+#define TETRA_LOCK_DROPPED 16    /* this chunk dropped the channel */
+#define TETRA_LOCK_SEARCHING 32  /* state.searching after the chunk */
+#define TETRA_ETSI_LOCK_NUM_DEFAULT 1        /* a stated choice, backed by the table of §5.28 */
+#define TETRA_ETSI_LOCK_DEN_DEFAULT 2        /* a stated choice, backed by the table of §5.28 */
+#define TETRA_ETSI_LOCK_WEAK_DEFAULT 8       /* a stated choice, backed by the table of §5.28 */
+#define TETRA_ETSI_LOCK_NMIN_DEFAULT 64      /* a stated choice, backed by the table of §5.28 */
+#define TETRA_ETSI_LOCK_PATIENCE_DEFAULT 1   /* a stated choice, backed by the table of §5.28 */
+int tetra_etsi_lock(tetra_ctx *ctx, const int8_t *softbits, const int32_t *nsym, size_t C, size_t ostride /*symbols*/,
+                    int32_t num, int32_t den, int32_t weak, int32_t nmin, int32_t patience,
+                    tetra_etsi_track *track /*[C] in/out*/, tetra_etsi_lock_state *state /*[C] in/out*/,
+                    int32_t *rec /*[C][TETRA_LOCK_FIELDS] out*/);
+
 /* ---------------------------------------------------------------- cell vote (new symbols of ABI version 2;
  * nothing existing changed shape).  tetra_lmac_etsi_acquire and _acquire_groups let the LAST CRC-good BSCH
  * set a cell: one false CRC pass on a badly received block (2^-16 per failed block), or a neighbour

@@ -123,6 +123,16 @@ ETSI_ASSIGN_SLOT = __import__("numpy").dtype([("since", "<i8"), ("last", "<i8"),
 ETSI_ASSIGN = __import__("numpy").dtype([("bit0", "<i8"), ("expired", "<i4"), ("released", "<i4"),
                                         ("slot", ETSI_ASSIGN_SLOT, (4,))])
 
+# tetra_etsi_lock (include/tetra_hip.h): struct tetra_etsi_lock_state, the record, its flag bits and the
+# defaults (stated choices, backed by the table of DESIGN.md §5.28)
+ETSI_LOCK_STATE = __import__("numpy").dtype([("searching", "<i4"), ("bad_run", "<i4"), ("relocks", "<i4"),
+                                            ("chunks", "<i4"), ("reserved", "<i4", (4,))])
+LOCK_SMIN, LOCK_SMAX, LOCK_N, LOCK_WEAK, LOCK_FLAGS, LOCK_BAD_RUN, LOCK_RELOCKS = range(7)
+LOCK_FIELDS = 8
+LOCK_JUDGED, LOCK_BAD, LOCK_RAILED, LOCK_FRESH, LOCK_DROPPED, LOCK_SEARCHING = 1, 2, 4, 8, 16, 32
+(ETSI_LOCK_NUM_DEFAULT, ETSI_LOCK_DEN_DEFAULT, ETSI_LOCK_WEAK_DEFAULT, ETSI_LOCK_NMIN_DEFAULT,
+ ETSI_LOCK_PATIENCE_DEFAULT) = 1, 2, 8, 64, 1
+
 _lib = None
 _lib_lock = threading.Lock()
 _tls = threading.local()
@@ -190,6 +200,8 @@ def _bind(L):
         "tetra_demod_etsi_stream": (_i32, [_vp, ctypes.POINTER(EtsiPlan), _vp, _i32, _sz, _sz, _sz, ctypes.c_int,
                                            _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]),
         "tetra_lmac_etsi_stream": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "tetra_etsi_lock": (_i32, [_vp, _vp, _vp, _sz, _sz, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                   ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
         "tetra_lmac_etsi_vote_groups": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, ctypes.c_int32, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _vp, _vp]),
         "tetra_lmac_etsi_stream_vote": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp,

@@ -198,6 +198,14 @@ class TetraDecoder:
                              f"(max: {max_corr:.4f}, original: {threshold:.4f})")
         return (sync, max_corr) if return_max_corr else sync
 
+    def reset(self):
+        """A new capture (the hook a capture loop calls on a retune, beside SignalProcessor.reset()): in ETSI
+        mode the next decode() starts a new stream (EtsiLowerMac.reset_stream: no carried dibits, timebase,
+        fragments or assignments; the acquired cell is kept); the compat chain carries nothing between
+        chunks, so there it does nothing."""
+        if self.mode == "etsi" and self._etsi is not None:
+            self._etsi.reset_stream()
+
     # ------------------------------------------------------------------ frames
     def decode(self, symbols):
         """Sync cascade, slot slicing and burst parsing of one symbol stream (decoder.py:835-888)."""

@@ -851,6 +851,26 @@ class EtsiLowerMac:
         self._assign = None   # [C] tetra_etsi_assign_state: the carried assignments (follow=True)
         self._assign_last = None   # the state the last call left (decode_batch's is not carried)
 
+    def reset_channels(self, mask):
+        """The masked channels ([C] bool) start a new chain, the others go on: their carried dibits are
+        dropped (the burst scan starts at the next chunk's first dibit) and their timebase, its score, the
+        cell's score, the fragment chains and the assignments are cleared.  The cell (``cell_state``,
+        ``acquired``) is kept: a receiver that re-acquired its timing is still on the same carrier.  From
+        the next call on a reset channel's frames are those of a new EtsiLowerMac with the same options
+        that was handed the cell.  What EtsiStream(lock=True) reports in ``fresh`` goes here."""
+        mask = np.asarray(mask, bool)
+        if not mask.any():
+            return
+        R = _hip.ETSI_RESERVE
+        if self._rows is not None and len(mask) == self._rows[1].shape[0]:
+            srow, hrow, lead = self._rows
+            srow[mask, :2 * R] = 0
+            hrow[mask, :R] = 0
+            lead[mask] = 2 * R
+        for a in (self._tdma, self.tdma_score, self.cell_score, self._frag, self._assign, self._lost):
+            if a is not None and len(a) == len(mask):
+                a[mask] = np.zeros((), a.dtype)
+
     @property
     def assign_stats(self):
         """follow=True: dict(expired [C], released [C]) -- assignments that ended after the hold time without
@@ -966,12 +986,16 @@ class EtsiLowerMac:
             self._lost += np.maximum(sd.ndone - SDU_MAXD, 0)
         return frames
 
-    def decode_stream(self, soft, hard, nsym, cells=None):
+    def decode_stream(self, soft, hard, nsym, cells=None, fresh=None):
         """decode_batch for consecutive chunks of C continuous streams (EtsiStream.demod rows):
         each channel's dibits the previous call left unconsumed -- from the first bit its burst scan
         did not examine -- go in front of this chunk's, and the scan resumes there
         (tetra_lmac_etsi_stream), so a burst across the seam is decoded whole.  Positions are
-        relative to this chunk's first dibit (negative: the burst began in the carried tail)."""
+        relative to this chunk's first dibit (negative: the burst began in the carried tail).
+        ``fresh`` ([C] bool, EtsiStream.fresh): the channels whose rows start a new chain
+        (reset_channels, applied before the call)."""
+        if fresh is not None:
+            self.reset_channels(fresh)
         soft = np.ascontiguousarray(soft, np.int8)
         hard = np.ascontiguousarray(hard, np.uint8)
         nsym = np.ascontiguousarray(nsym, np.int32)
@@ -1039,5 +1063,6 @@ class EtsiLowerMac:
         soft = np.zeros((1, 2 * smax), np.int8)
         soft[0, :2 * n] = np.asarray(sb, np.int8)[:2 * n]
         if stream:
-            return self.decode_stream(soft, hard, np.array([n + 1], np.int32))[0]
+            new = bool(getattr(symbols, "new_stream", False))   # the receiver re-acquired (EtsiReceiver(relock=True))
+            return self.decode_stream(soft, hard, np.array([n + 1], np.int32), fresh=[True] if new else None)[0]
         return self.decode_batch(soft, hard, np.array([n + 1], np.int32))[0]

@@ -94,13 +94,17 @@ class SoftSymbols(np.ndarray):
     """uint8 hard dibit symbols (what process() returns) that also carry ``soft_bits`` (int8, >0 = 0)
     so TetraDecoder(mode='etsi').decode() can run the soft-decision Viterbi on them."""
 
-    def __new__(cls, hard, soft_bits):
+    def __new__(cls, hard, soft_bits, new_stream=False):
         obj = np.asarray(hard, np.uint8).view(cls)
         obj.soft_bits = soft_bits
+        # True: these symbols start a new chain (the receiver re-acquired its timing, EtsiReceiver(relock=True)):
+        # TetraDecoder(mode='etsi').decode() drops the dibits it carried from the chunks before
+        obj.new_stream = bool(new_stream)
         return obj
 
     def __array_finalize__(self, obj):
         self.soft_bits = getattr(obj, "soft_bits", None)
+        self.new_stream = getattr(obj, "new_stream", False)
 
 
 RESERVE, MARGIN = _hip.ETSI_RESERVE, _hip.ETSI_MARGIN
@@ -153,10 +157,29 @@ class EtsiStream:
     phase is continuous too.  Row c of the outputs holds the carried last symbol of the previous
     chunk first (once the channel's loop is acquired), so its nsym-1 dibits start with the one across
     the seam -- exactly the row layout demod_batch returns, ready for EtsiLowerMac.decode_stream.
-    oracle/etsi.py Stream restates it."""
+    oracle/etsi.py Stream restates it.
 
-    def __init__(self, sample_rate=2.4e6, channels=1):
+    ``lock=True`` (off by default) runs the loss-of-lock monitor (tetra_etsi_lock) after every demod:
+    a channel whose chunk reads as out of lock has its ``track.acquired`` cleared, so its next chunk
+    acquires afresh.  After a call ``lock_records`` [C, 8] holds the monitor's records, ``lock_state``
+    its carried state, ``dropped`` [C] the channels this call dropped and ``fresh`` [C] the rows of this
+    call that start a new chain (their demod ran with acquired = 0: hand them to
+    EtsiLowerMac.decode_stream(fresh=...)).  ``lock_patience`` and ``lock_ratio`` = (num, den) replace the
+    defaults (TETRA_ETSI_LOCK_*_DEFAULT).  ``redo=True``: a call that dropped a channel
+    repeats its demod on the same window, from the track as it stood before the call with acquired = 0
+    for the dropped channels -- before the history and the window counters advance -- and replaces
+    all outputs; the kernels are deterministic, so every other channel's outputs come out bit for bit
+    as they were, and the monitor judges the redone rows as fresh chunks (one extra demod in calls that
+    drop a channel, none otherwise).  tests/_etsi_lock_model.py LockedStream restates it."""
+
+    def __init__(self, sample_rate=2.4e6, channels=1, lock=False, lock_patience=None, lock_ratio=None, redo=False):
         self.sample_rate = sample_rate
+        self.lock, self.redo = bool(lock), bool(redo)
+        if self.redo and not self.lock:
+            raise ValueError("redo=True repeats the demod of channels the monitor dropped: it needs lock=True")
+        num, den = (_hip.ETSI_LOCK_NUM_DEFAULT, _hip.ETSI_LOCK_DEN_DEFAULT) if lock_ratio is None else lock_ratio
+        self.lock_args = (int(num), int(den), _hip.ETSI_LOCK_WEAK_DEFAULT, _hip.ETSI_LOCK_NMIN_DEFAULT,
+                          _hip.ETSI_LOCK_PATIENCE_DEFAULT if lock_patience is None else int(lock_patience))
         self.plan = etsi_plan(sample_rate)
         # input samples kept per channel: what a window of this plan can re-read (1447 at 2.4 MSps, up
         # to 6046 at the rates rate_design serves)
@@ -170,6 +193,18 @@ class EtsiStream:
         self.x_total = self.y_done = 0
         self.hist = None
         self.diag = None
+        self.lock_state = np.zeros(self.C, _hip.ETSI_LOCK_STATE)
+        self.lock_records = np.zeros((self.C, _hip.LOCK_FIELDS), np.int32)
+        self.dropped = np.zeros(self.C, bool)
+        self.fresh = np.zeros(self.C, bool)
+
+    def _monitor(self, soft, ns, smax):
+        """tetra_etsi_lock on a demod's outputs: the records (track and lock_state updated)."""
+        c = _hip.ctx()
+        rec = np.zeros((self.C, _hip.LOCK_FIELDS), np.int32)
+        c.check(c.lib.tetra_etsi_lock(c.handle, _hip.ptr(soft), _hip.ptr(ns), self.C, smax, *self.lock_args,
+                                      _hip.ptr(self.track), _hip.ptr(self.lock_state), _hip.ptr(rec)), "tetra_etsi_lock")
+        return rec
 
     def demod(self, iq, freq_offsets=None, row_pad=0):
         """[C, n] complex or [C, n, 2] int16 SC16 (n even) -> (hard [C, smax] u8, soft_bits
@@ -220,14 +255,37 @@ class EtsiStream:
             dwin = wide
         _, M2, sm = lengths(self.plan, W)
         smax = max(sm + 1, 2)
-        sym = np.zeros((self.C, smax), np.complex64)
-        soft = np.zeros((self.C, 2 * smax), np.int8)
-        hard = np.zeros((self.C, smax), np.uint8)
-        ns = np.zeros(self.C, np.int32)
-        diag = np.zeros((self.C, 4), np.float32)
-        c.check(c.lib.tetra_demod_etsi_stream(c.handle, self.plan, _hip.ptr(dwin), fmt, self.C, dwin.shape[1], W, int(yoff),
-                                              _hip.ptr(self.track), _hip.ptr(sym), _hip.ptr(soft), _hip.ptr(hard),
-                                              _hip.ptr(ns), smax, smax, _hip.ptr(diag)), "tetra_demod_etsi_stream")
+
+        def run():
+            sym = np.zeros((self.C, smax), np.complex64)
+            soft = np.zeros((self.C, 2 * smax), np.int8)
+            hard = np.zeros((self.C, smax), np.uint8)
+            ns = np.zeros(self.C, np.int32)
+            diag = np.zeros((self.C, 4), np.float32)
+            c.check(c.lib.tetra_demod_etsi_stream(c.handle, self.plan, _hip.ptr(dwin), fmt, self.C, dwin.shape[1], W,
+                                                  int(yoff), _hip.ptr(self.track), _hip.ptr(sym), _hip.ptr(soft),
+                                                  _hip.ptr(hard), _hip.ptr(ns), smax, smax, _hip.ptr(diag)),
+                    "tetra_demod_etsi_stream")
+            return hard, soft, sym, ns, diag
+
+        track0 = self.track.copy()
+        self.fresh = track0["acquired"] == 0
+        hard, soft, sym, ns, diag = run()
+        if self.lock:
+            state0 = self.lock_state.copy()
+            self.lock_records = self._monitor(soft, ns, smax)
+            self.dropped = (self.lock_records[:, _hip.LOCK_FLAGS] & _hip.LOCK_DROPPED) != 0
+            if self.redo and self.dropped.any():
+                # the same window again, the dropped channels acquiring: the track of before the call, and the
+                # monitor's state of before it for the channels it did not drop (their chunk is judged again,
+                # to the same end); a dropped channel keeps its new state, its chunk counted once
+                self.track[:] = track0
+                self.track["acquired"][self.dropped] = 0
+                self.lock_state["chunks"][self.dropped] = state0["chunks"][self.dropped]
+                self.lock_state[~self.dropped] = state0[~self.dropped]
+                self.fresh = self.track["acquired"] == 0
+                hard, soft, sym, ns, diag = run()
+                self.lock_records = self._monitor(soft, ns, smax)
         keep = min(self.hist_len, win.shape[1])
         self.hist = np.ascontiguousarray(win[:, win.shape[1] - keep:])
         self.x_total += n
@@ -237,8 +295,13 @@ class EtsiStream:
 
 
 class EtsiReceiver:
-    def __init__(self, sample_rate=2.4e6):
+    """relock=True (off by default): process() streams with the loss-of-lock monitor on
+    (EtsiStream(lock=True, redo=True)); a chunk on which the receiver re-acquired its timing returns
+    symbols with ``new_stream`` set, which TetraDecoder(mode='etsi').decode() honours."""
+
+    def __init__(self, sample_rate=2.4e6, relock=False):
         self.sample_rate = sample_rate
+        self.relock = bool(relock)
         self.plan = etsi_plan(sample_rate)
         self.diag = None
         self._stream = None
@@ -304,12 +367,14 @@ class EtsiReceiver:
             if len(x) == 0:
                 return SoftSymbols(np.zeros(0, np.uint8), np.zeros(0, np.int8)), np.zeros(0, np.complex64)
             if self._stream is None:
-                self._stream = EtsiStream(self.sample_rate, 1)
+                self._stream = EtsiStream(self.sample_rate, 1, lock=self.relock, redo=self.relock)
+            first = self._stream.x_total == 0   # a stream's first chunk is a new chain for the decoder anyway
             hard, soft, sym, ns = self._stream.demod(x[None, :], [freq_offset] if freq_offset else None)
             self.diag = self._stream.diag
             n = int(ns[0])
             nd = max(0, n - 1)
-            return SoftSymbols(hard[0, :nd].copy(), soft[0, :2 * nd].copy()), sym[0, :n].copy()
+            new = self.relock and not first and bool(self._stream.fresh[0])
+            return SoftSymbols(hard[0, :nd].copy(), soft[0, :2 * nd].copy(), new_stream=new), sym[0, :n].copy()
         if freq_offset and len(x):   # AFC mixer on the GPU (same kernel as frequency_shift)
             from tetraear.signal.processor import mixer_coefficient
             out = np.empty(len(x), np.complex128)

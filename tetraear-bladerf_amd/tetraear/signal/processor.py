@@ -203,8 +203,11 @@ def mixer_coefficient(freq_offset):
 class SignalProcessor:
     """Processes raw IQ samples for TETRA demodulation (processor.py:18)."""
 
-    def __init__(self, sample_rate=2.4e6, mode=None, decimator=None):
+    def __init__(self, sample_rate=2.4e6, mode=None, decimator=None, relock=None):
         self.sample_rate = sample_rate
+        # ETSI mode only, off by default (relock=True or TETRAEAR_ETSI_RELOCK=1): process() watches the
+        # stream for loss of lock and re-acquires the timing (EtsiReceiver(relock=True))
+        self.relock = os.environ.get("TETRAEAR_ETSI_RELOCK", "0") == "1" if relock is None else bool(relock)
         self.symbol_rate = SYMBOL_RATE
         self.samples_per_symbol = int(sample_rate / self.symbol_rate)
         self.symbols = None
@@ -501,8 +504,15 @@ class SignalProcessor:
     def _etsi_rx(self):
         if self._etsi is None:
             from tetraear.signal.etsi import EtsiReceiver
-            self._etsi = EtsiReceiver(self.sample_rate)
+            self._etsi = EtsiReceiver(self.sample_rate, relock=self.relock)
         return self._etsi
+
+    def reset(self):
+        """A new capture (the hook a capture loop calls on a retune): in ETSI mode the next process()
+        acquires its timing afresh (EtsiReceiver.reset); the compat chain carries nothing between
+        chunks, so there it does nothing."""
+        if self.mode == "etsi" and self._etsi is not None:
+            self._etsi.reset()
 
 
 def ctypes_int():
